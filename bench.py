@@ -17,6 +17,12 @@ Launch (driver contract):
 
 Other BASELINE configs are reachable with --config {allreduce,linreg,
 ring,alltoall} for self-measurement; the driver uses the default.
+
+A plain run sets up, warms up, times the steps and prints the JSON line.
+--full adds the secondary measurements (today: the N=1 default-path
+timing recorded next to the headline). --dump-outputs DIR writes what the
+last timed step returned to its caller as DIR/<name>.npy; inputs are
+seeded, so two builds can be compared output for output.
 """
 
 import argparse
@@ -25,6 +31,13 @@ import os
 import time
 
 import torch
+
+SEED = 20240229
+# --dump-outputs: arrays above this many elements are written as a fixed
+# seeded sample (4 Mi float32 = 16 MiB each; every config returns at most
+# three arrays, so a dump stays under 64 MB)
+DUMP_MAX_ELEMS = 1 << 22
+DUMP_MAX_BYTES = 64 * 1000 * 1000
 
 
 def setup_world(args):
@@ -65,23 +78,63 @@ def sync(device):
 
 
 def time_steps(step_fn, steps, warmup, device):
+    """Wall time of `steps` calls of step_fn, each run to completion.
+
+    Every step ends in a device synchronize. The collectives run on side
+    streams and mark their buffers with recordStream, so the caching
+    allocator cannot reuse a step's tensors before the device has finished
+    it. A host that queues steps without waiting therefore takes fresh
+    device memory for every queued step, and ms_per_step then measures
+    allocation and depends on --steps. With the synchronize the working
+    set is fixed after warm-up and ms_per_step does not depend on the
+    number of steps (measurements: profiles/bench_steps_stability.md).
+    """
     import torch.distributed as dist
 
     for _ in range(warmup):
         step_fn()
-    sync(device)
+        sync(device)
     dist.barrier()
     sync(device)
     t0 = time.perf_counter()
-    for _ in range(steps):
+    # only the last step's return value is kept, so the steps before it
+    # free their results exactly as a caller that drops them would
+    for _ in range(steps - 1):
         step_fn()
+        sync(device)
+    outputs = step_fn()
     sync(device)
     elapsed = time.perf_counter() - t0
     dist.barrier()
     # MAX over ranks
     t = torch.tensor([elapsed], dtype=torch.float64)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    return float(t.item())
+    return float(t.item()), outputs
+
+
+def dump_outputs(outputs, out_dir):
+    """Write each tensor of `outputs` as <out_dir>/<name>.npy (float32, or
+    float64 for double tensors). Large tensors are reduced to the same
+    seeded sample of flat indices in every run."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, x in outputs.items():
+        x = x.detach().reshape(-1)
+        if x.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(SEED)
+            idx = torch.randint(0, x.numel(), (DUMP_MAX_ELEMS,), generator=g)
+            idx = idx.sort().values.to(x.device)
+            if x.element_size() == 1:  # fp8: gather the raw bytes
+                x = x.view(torch.uint8)[idx].view(x.dtype)
+            else:
+                x = x[idx]
+        x = x.to(torch.float64 if x.dtype == torch.float64 else torch.float32)
+        a = x.cpu().numpy()
+        total += a.nbytes
+        assert total <= DUMP_MAX_BYTES, "dump exceeds 64 MB"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def bench_allreduce(m4a, comm, device, args):
@@ -95,8 +148,9 @@ def bench_allreduce(m4a, comm, device, args):
         t.grad = None
         r = comm.Allreduce(t, m4a.MPI_SUM)
         r.backward(grad_seed)
+        return {"allreduce_out": r, "input_grad": t.grad}
 
-    elapsed = time_steps(step, args.steps, args.warmup, device)
+    elapsed, outputs = time_steps(step, args.steps, args.warmup, device)
     t_step = elapsed / args.steps
 
     config = {
@@ -106,7 +160,7 @@ def bench_allreduce(m4a, comm, device, args):
         "seq_len": None,
         "parallelism": f"dp{comm.size}",
     }
-    if comm.size == 1 and device.type == "cuda":
+    if args.full and comm.size == 1 and device.type == "cuda":
         # The timed region holds a REAL ncclAllReduce (force_full_path);
         # at nranks=1 RCCL implements it as an internal copy whose speed
         # varies wildly across boxes (profiles/rccl_1rank_box_variance.md:
@@ -116,7 +170,7 @@ def bench_allreduce(m4a, comm, device, args):
         m4a = __import__("mpi4torch_amd")
         m4a._C.force_full_path(False)
         try:
-            fp_elapsed = time_steps(step, 5, 2, device)
+            fp_elapsed, _ = time_steps(step, 5, 2, device)
             config["n1_default_path_ms"] = round(fp_elapsed / 5 * 1e3, 3)
             config["n1_note"] = (
                 "value times RCCL's nranks=1 internal copy "
@@ -132,7 +186,7 @@ def bench_allreduce(m4a, comm, device, args):
         "value": comm.size * 2 * nbytes / t_step / 1e9,
         "unit": "GB/s",
         "config": config,
-    }, t_step
+    }, t_step, outputs
 
 
 def bench_linreg(m4a, comm, device, args):
@@ -151,8 +205,12 @@ def bench_linreg(m4a, comm, device, args):
         loss = model.loss(x, y)
         loss.backward()
         opt.step()
+        out = {"loss": loss}
+        for i, p in enumerate(model.parameters()):
+            out[f"param{i}"] = p
+        return out
 
-    elapsed = time_steps(step, args.steps, args.warmup, device)
+    elapsed, outputs = time_steps(step, args.steps, args.warmup, device)
     t_step = elapsed / args.steps
     return {
         "metric": "linreg_steps_per_s",
@@ -164,7 +222,7 @@ def bench_linreg(m4a, comm, device, args):
             "seq_len": None,
             "parallelism": f"dp{comm.size}",
         },
-    }, t_step
+    }, t_step, outputs
 
 
 def bench_ring(m4a, comm, device, args):
@@ -185,8 +243,9 @@ def bench_ring(m4a, comm, device, args):
         res = comm.Wait(m4a.JoinDummiesHandle(req, [req2.dummy]))
         res2 = comm.Wait(m4a.JoinDummiesHandle(req2, [res]))
         res2.backward(grad_seed)
+        return {"ring_out": res2, "input_grad": t.grad}
 
-    elapsed = time_steps(step, args.steps, args.warmup, device)
+    elapsed, outputs = time_steps(step, args.steps, args.warmup, device)
     t_step = elapsed / args.steps
     nbytes = n * 4
     return {
@@ -199,7 +258,7 @@ def bench_ring(m4a, comm, device, args):
             "seq_len": None,
             "parallelism": f"ring{comm.size}",
         },
-    }, t_step
+    }, t_step, outputs
 
 
 def bench_alltoall(m4a, comm, device, args):
@@ -219,8 +278,9 @@ def bench_alltoall(m4a, comm, device, args):
         t.grad = None
         r = comm.Alltoallv(t, 1, 0, counts, counts)
         r.backward(grad_seed)
+        return {"alltoall_out": r, "input_grad": t.grad}
 
-    elapsed = time_steps(step, args.steps, args.warmup, device)
+    elapsed, outputs = time_steps(step, args.steps, args.warmup, device)
     t_step = elapsed / args.steps
     nbytes = rows * 4096
     return {
@@ -233,7 +293,7 @@ def bench_alltoall(m4a, comm, device, args):
             "seq_len": None,
             "parallelism": f"ep{comm.size}",
         },
-    }, t_step
+    }, t_step, outputs
 
 
 BENCHES = {
@@ -256,20 +316,36 @@ def main():
                    help="run every BASELINE config; write all JSON records "
                         "to gpurun_out/bench_all.jsonl, print the headline "
                         "(allreduce) line last")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements (N=1 "
+                        "default-path timing next to the headline)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the arrays the last timed step returned as "
+                        "DIR/<name>.npy (seeded sample of large ones)")
     args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
 
     m4a, rank, world, device = setup_world(args)
     comm = m4a.COMM_WORLD
     assert comm.size == world
 
+    def run_config(name):
+        # every config starts from the same seed, so its inputs are the
+        # same in every run with the same arguments, --all-configs or not
+        torch.manual_seed(SEED + rank)
+        return BENCHES[name](m4a, comm, device, args)
+
     extra_records = []
     if args.all_configs:
         for name in ("linreg", "ring", "alltoall"):
-            r, ts = BENCHES[name](m4a, comm, device, args)
+            r, ts, _ = run_config(name)
             r["ms_per_step"] = round(ts * 1e3, 3)
             extra_records.append(r)
         args.config = "allreduce"
-    result, t_step = BENCHES[args.config](m4a, comm, device, args)
+    result, t_step, outputs = run_config(args.config)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(outputs, args.dump_outputs)
     # RCCL's version banner is written through C stdio, which is fully
     # buffered on a pipe and flushes at exit — AFTER our JSON. Flush it now
     # so the JSON line is the last thing on stdout.

@@ -70,5 +70,8 @@ def test_gpu_multi_spmd():
 
 def test_gpu_multi_launch_cpu_dryrun():
     # same worker, same torchrun launch path, CPU/gloo at nproc=2 — the
-    # de-risking dry run for the multi-GPU battery
-    _launch(2, timeout=600)
+    # de-risking dry run for the multi-GPU battery. Hide any GPU from the
+    # workers: on a box with one GPU they would otherwise pick cuda and
+    # rank 1 would ask for a device that is not there.
+    _launch(2, timeout=600, extra_env={"HIP_VISIBLE_DEVICES": "-1",
+                                       "CUDA_VISIBLE_DEVICES": "-1"})
