@@ -44,6 +44,7 @@ static auto communicator_class =
         .def("GetRank", &Communicator::GetRank)
         .def("GetSize", &Communicator::GetSize)
         .def("Allreduce", &Communicator::Allreduce)
+        .def("AllreduceCompressed", &Communicator::AllreduceCompressed)
         .def("Bcast_", &Communicator::Bcast_)
         .def("Reduce_", &Communicator::Reduce_)
         .def("Gather", &Communicator::Gather)
@@ -104,6 +105,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("_bitwise_reduce", &m4a::debug_bitwise_reduce);
   m.def("_fp8_reduce", &m4a::debug_fp8_reduce);
   m.def("_pairloc_reduce", &m4a::debug_pairloc_reduce);
+  m.def("_mx8_quantize", &m4a::debug_mx8_quantize);
+  m.def("_mx8_reduce", &m4a::debug_mx8_reduce);
+  m.def("_mx8_dequantize", &m4a::debug_mx8_dequantize, py::arg("payload"),
+        py::arg("scales"), py::arg("numel"), py::arg("dtype"),
+        py::arg("out") = c10::optional<at::Tensor>());
   m.def("reload_config", &m4a::reload_config_from_env);
 
   m.def("_rccl_version", []() {

@@ -64,4 +64,23 @@ void launch_pairloc_reduce(const void* in, void* out, int64_t n_pairs,
 void launch_fp8_reduce(const void* in, void* out, int64_t n_elems,
                        int nranks, int op, bool e5m2, hipStream_t stream);
 
+// mxfp8 codec (csrc/mx8_kernels.hip): groups of 32 consecutive elements ->
+// 32 OCP e4m3fn payload bytes + one E8M0 scale byte (255 = non-finite
+// group). The rule is defined by the torch composite in csrc/ops.cpp; the
+// kernels match it byte for byte. dtype codes: 0=f32 1=bf16 2=f16.
+//
+// Quantize n_elems elements: payload gets ceil(n/32)*32 bytes (the partial
+// last group is zero-padded), scales ceil(n/32) bytes.
+void launch_mx8_quantize(const void* in, void* payload, void* scales,
+                         int64_t n_elems, int dtype, hipStream_t stream);
+// Reduce nranks copies of n_groups groups: payload_in [nranks][n_groups*32],
+// scales_in [nranks][n_groups]. Sum in rank order on dequantized fp32
+// values, one requantization.
+void launch_mx8_reduce(const void* payload_in, const void* scales_in,
+                       void* payload_out, void* scales_out, int64_t n_groups,
+                       int nranks, hipStream_t stream);
+// Dequantize into exactly n_elems elements of the given dtype (RNE).
+void launch_mx8_dequantize(const void* payload, const void* scales, void* out,
+                           int64_t n_elems, int dtype, hipStream_t stream);
+
 } // namespace m4a

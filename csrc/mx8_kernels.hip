@@ -1,0 +1,532 @@
+// mxfp8 codec kernels for gfx950: the compressed-allreduce wire format.
+//
+// Format: groups of 32 consecutive elements; each group is 32 OCP e4m3fn
+// payload bytes plus one E8M0 scale byte (33/32 byte per element). The
+// codec rule is normative and defined by the torch composite in
+// csrc/ops.cpp (mx8_quantize_groups / mx8_dequantize_groups); these kernels
+// reproduce it bit for bit:
+//   * amax over |x| is taken on the IEEE bit patterns (monotone for finite
+//     values; anything >= 0x7f800000 is inf/NaN -> scale 255, zero payload);
+//   * the shared exponent E comes from the exponent/mantissa fields
+//     (frexp arithmetic, no log2f): amax = m*2^k, m in [0.5,1):
+//     E = k-9 if m <= 0.875 else k-8, clamped to [-127,127];
+//   * scaling is ldexpf (exact power-of-two scale), the conversion is the
+//     hardware RNE f32->e4m3 of hip_fp8.h, which cannot saturate because
+//     amax*2^-E <= 448 by construction.
+//
+// Three streaming kernels, all 256-thread workgroups, grid-stride, 16-byte
+// accesses on the wide side, nontemporal (every byte is touched once):
+//   quantize   : 8 lanes x 16 B per fp32 group, 4 lanes x 16 B per 16-bit
+//                group; amax crosses the lanes with 3 / 2 xor-shuffles;
+//                payload leaves as packed dwords; scale bytes are gathered
+//                across the wave so one lane stores four at once.
+//   reduce     : sibling of fp8_reduce_kernel — dwordx4 payload loads
+//                (16 elements per lane, 2 lanes per group), 16 fp32
+//                accumulators, P copies summed in rank order on dequantized
+//                values, requantization fused (amax crosses the lane pair).
+//   dequantize : mirror of quantize; writes exactly N elements.
+// Each has a one-thread-per-group scalar twin for base pointers that miss
+// the vector alignment (e.g. a contiguous x[1:] view); the partial last
+// group of the vector kernels goes through the same scalar group routine.
+
+#include <hip/hip_runtime.h>
+#include <hip/hip_fp8.h>
+#include "kernels.hpp"
+
+namespace m4a {
+
+namespace {
+
+typedef unsigned int v4u __attribute__((ext_vector_type(4)));
+typedef unsigned int v2u __attribute__((ext_vector_type(2)));
+typedef unsigned char u8;
+
+constexpr unsigned kInfBits = 0x7f800000u;
+constexpr unsigned kQNaNBits = 0x7fc00000u;
+
+enum { kF32 = 0, kBF16 = 1, kF16 = 2 };
+
+template <int K> struct Elem { using type = float; };
+template <> struct Elem<kBF16> { using type = unsigned short; };
+template <> struct Elem<kF16> { using type = unsigned short; };
+
+__device__ inline float e4m3_to_f32(u8 b) {
+  __hip_fp8_e4m3 v;
+  v.__x = b;
+  return float(v);
+}
+
+__device__ inline u8 f32_to_e4m3(float f) {
+  __hip_fp8_e4m3 v(f);
+  return v.__x;
+}
+
+// ---- element <-> f32 ----------------------------------------------------
+
+template <int K>
+__device__ inline float elem_to_f32(typename Elem<K>::type e);
+template <>
+__device__ inline float elem_to_f32<kF32>(float e) { return e; }
+template <>
+__device__ inline float elem_to_f32<kBF16>(unsigned short e) {
+  return __uint_as_float((unsigned)e << 16);
+}
+template <>
+__device__ inline float elem_to_f32<kF16>(unsigned short e) {
+  return (float)__builtin_bit_cast(_Float16, e);
+}
+
+// RNE to the output dtype (bf16: the usual bias trick, NaN -> 0x7fc0)
+template <int K>
+__device__ inline typename Elem<K>::type f32_to_elem(float f);
+template <>
+__device__ inline float f32_to_elem<kF32>(float f) { return f; }
+template <>
+__device__ inline unsigned short f32_to_elem<kBF16>(float f) {
+  unsigned u = __float_as_uint(f);
+  if ((u & 0x7fffffffu) > kInfBits) return 0x7fc0;
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return (unsigned short)(u >> 16);
+}
+template <>
+__device__ inline unsigned short f32_to_elem<kF16>(float f) {
+  return __builtin_bit_cast(unsigned short, (_Float16)f);
+}
+
+// 16 bytes of input -> 4 (fp32) or 8 (16-bit) floats
+template <int K, int EPL>
+__device__ inline void unpack16(const v4u& w, float (&x)[EPL]) {
+  if constexpr (K == kF32) {
+    for (int d = 0; d < 4; ++d) x[d] = __uint_as_float(w[d]);
+  } else {
+    for (int d = 0; d < 4; ++d) {
+      x[2 * d] = elem_to_f32<K>((unsigned short)(w[d] & 0xffffu));
+      x[2 * d + 1] = elem_to_f32<K>((unsigned short)(w[d] >> 16));
+    }
+  }
+}
+
+template <int K, int EPL>
+__device__ inline v4u pack16(const float (&x)[EPL]) {
+  v4u w;
+  if constexpr (K == kF32) {
+    for (int d = 0; d < 4; ++d) w[d] = __float_as_uint(x[d]);
+  } else {
+    for (int d = 0; d < 4; ++d) {
+      w[d] = (unsigned)f32_to_elem<K>(x[2 * d]) |
+             ((unsigned)f32_to_elem<K>(x[2 * d + 1]) << 16);
+    }
+  }
+  return w;
+}
+
+// ---- the codec rule -----------------------------------------------------
+
+// amax_bits: max over the group of (bits & 0x7fffffff). Returns the scale
+// byte; *E receives the shared exponent (unused when the byte is 255).
+__device__ inline int mx8_scale_byte(unsigned amax_bits, int* E) {
+  if (amax_bits >= kInfBits) {
+    *E = 0;
+    return 255;
+  }
+  const int e = (int)(amax_bits >> 23);
+  const unsigned f = amax_bits & 0x7fffffu;
+  int ex;
+  if (amax_bits == 0) {
+    ex = 0;
+  } else if (e == 0) {
+    ex = -127;  // fp32 subnormal amax: k <= -126, k-8 clamps
+  } else {
+    // amax = 1.f * 2^(e-127) = m * 2^(e-126), m = 1.f/2; m <= 0.875 <=>
+    // f <= 0x600000
+    ex = (e - 126) - (f <= 0x600000u ? 9 : 8);
+    if (ex < -127) ex = -127;
+  }
+  *E = ex;
+  return ex + 127;
+}
+
+__device__ inline float mx8_dequant(u8 b, int sb) {
+  return sb == 255 ? __uint_as_float(kQNaNBits)
+                   : ldexpf(e4m3_to_f32(b), sb - 127);
+}
+
+template <int N>
+__device__ inline unsigned amax_bits_of(const float (&x)[N]) {
+  unsigned a = 0;
+  for (int k = 0; k < N; ++k) {
+    const unsigned b = __float_as_uint(x[k]) & 0x7fffffffu;
+    a = b > a ? b : a;
+  }
+  return a;
+}
+
+// four values -> one packed payload dword
+__device__ inline unsigned quant4(float a, float b, float c, float d, int E) {
+  return (unsigned)f32_to_e4m3(ldexpf(a, -E)) |
+         ((unsigned)f32_to_e4m3(ldexpf(b, -E)) << 8) |
+         ((unsigned)f32_to_e4m3(ldexpf(c, -E)) << 16) |
+         ((unsigned)f32_to_e4m3(ldexpf(d, -E)) << 24);
+}
+
+// Gather the wave's scale bytes (group j's byte lives in lane j*LPG) so
+// lane l stores groups 4l..4l+3 as one dword. Every lane of the wave must
+// call this (the shuffles read across groups). gbase: first group of the
+// wave; ngroups: bound of the scales array.
+template <int LPG>
+__device__ inline void store_scales(u8* __restrict__ sc, long long gbase,
+                                    long long ngroups, int sb, int lane) {
+  constexpr int GPW = 64 / LPG;
+  unsigned packed = 0;
+  for (int k = 0; k < 4; ++k) {
+    const int src = ((lane * 4 + k) * LPG) & 63;
+    packed |= ((unsigned)__shfl(sb, src) & 0xffu) << (8 * k);
+  }
+  if (lane < GPW / 4) {
+    const long long g = gbase + 4 * lane;
+    u8* p = sc + g;
+    if (g + 4 <= ngroups && ((uintptr_t)p & 3) == 0) {
+      __builtin_nontemporal_store(packed, reinterpret_cast<unsigned*>(p));
+    } else {
+      for (int k = 0; k < 4; ++k) {
+        if (g + k < ngroups) p[k] = (u8)(packed >> (8 * k));
+      }
+    }
+  }
+}
+
+// ---- scalar group routines (any alignment, partial groups) --------------
+
+__device__ inline void encode_group_scalar(const float (&x)[32],
+                                           u8* __restrict__ pay,
+                                           u8* __restrict__ sc) {
+  int E;
+  const int sb = mx8_scale_byte(amax_bits_of(x), &E);
+  for (int k = 0; k < 32; ++k) {
+    pay[k] = sb == 255 ? (u8)0 : f32_to_e4m3(ldexpf(x[k], -E));
+  }
+  *sc = (u8)sb;
+}
+
+template <int K>
+__device__ inline void quant_group_scalar(
+    const typename Elem<K>::type* __restrict__ in, int cnt,
+    u8* __restrict__ pay, u8* __restrict__ sc) {
+  float x[32];
+  for (int k = 0; k < 32; ++k) {
+    x[k] = k < cnt ? elem_to_f32<K>(in[k]) : 0.0f;
+  }
+  encode_group_scalar(x, pay, sc);
+}
+
+template <int K>
+__device__ inline void dequant_group_scalar(
+    const u8* __restrict__ pay, int sb, int cnt,
+    typename Elem<K>::type* __restrict__ out) {
+  for (int k = 0; k < 32; ++k) {
+    if (k < cnt) out[k] = f32_to_elem<K>(mx8_dequant(pay[k], sb));
+  }
+}
+
+// ---- quantize -----------------------------------------------------------
+
+template <int K>
+__global__ __launch_bounds__(256) void mx8_quantize_kernel(
+    const void* __restrict__ in, u8* __restrict__ pay, u8* __restrict__ sc,
+    long long nfull, long long N) {
+  using T = typename Elem<K>::type;
+  constexpr int LPG = K == kF32 ? 8 : 4;  // lanes per group
+  constexpr int EPL = 32 / LPG;           // elements per lane (16 B)
+  const long long total = nfull * LPG;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  const int lane = threadIdx.x & 63;
+  // wave-uniform trip count: the shuffles below need every lane present
+  for (long long i0 = (long long)blockIdx.x * blockDim.x + (threadIdx.x & ~63);
+       i0 < total; i0 += stride) {
+    const long long i = i0 + lane;
+    const bool act = i < total;
+    float x[EPL];
+    if (act) {
+      const v4u w =
+          __builtin_nontemporal_load(reinterpret_cast<const v4u*>(in) + i);
+      unpack16<K, EPL>(w, x);
+    } else {
+      for (int k = 0; k < EPL; ++k) x[k] = 0.0f;
+    }
+    unsigned a = amax_bits_of(x);
+    for (int m = 1; m < LPG; m <<= 1) {
+      const unsigned o = (unsigned)__shfl_xor((int)a, m);
+      a = o > a ? o : a;
+    }
+    int E;
+    const int sb = mx8_scale_byte(a, &E);
+    if (act) {
+      if constexpr (K == kF32) {
+        const unsigned o = sb == 255 ? 0u : quant4(x[0], x[1], x[2], x[3], E);
+        __builtin_nontemporal_store(o, reinterpret_cast<unsigned*>(pay) + i);
+      } else {
+        v2u o;
+        o[0] = sb == 255 ? 0u : quant4(x[0], x[1], x[2], x[3], E);
+        o[1] = sb == 255
+                   ? 0u
+                   : quant4(x[EPL - 4], x[EPL - 3], x[EPL - 2], x[EPL - 1], E);
+        __builtin_nontemporal_store(o, reinterpret_cast<v2u*>(pay) + i);
+      }
+    }
+    store_scales<LPG>(sc, i0 / LPG, nfull, sb, lane);
+  }
+  // zero-padded partial last group
+  const int tail = (int)(N - nfull * 32);
+  if (tail > 0 && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+    quant_group_scalar<K>(reinterpret_cast<const T*>(in) + nfull * 32, tail,
+                          pay + nfull * 32, sc + nfull);
+  }
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void mx8_quantize_kernel_scalar(
+    const void* __restrict__ in, u8* __restrict__ pay, u8* __restrict__ sc,
+    long long G, long long N) {
+  using T = typename Elem<K>::type;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < G;
+       g += stride) {
+    const long long left = N - g * 32;
+    quant_group_scalar<K>(reinterpret_cast<const T*>(in) + g * 32,
+                          left < 32 ? (int)left : 32, pay + g * 32, sc + g);
+  }
+}
+
+// ---- reduce -------------------------------------------------------------
+
+__global__ __launch_bounds__(256) void mx8_reduce_kernel(
+    const u8* __restrict__ pin, const u8* __restrict__ sin,
+    u8* __restrict__ pout, u8* __restrict__ sout, long long n,
+    long long nranks) {
+  const long long total = n * 2;  // 16-byte vectors per copy
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  const int lane = threadIdx.x & 63;
+  for (long long i0 = (long long)blockIdx.x * blockDim.x + (threadIdx.x & ~63);
+       i0 < total; i0 += stride) {
+    const long long i = i0 + lane;
+    const bool act = i < total;
+    const long long g = i >> 1;
+    float acc[16];
+    bool bad = false;
+    if (act) {
+      const v4u* base = reinterpret_cast<const v4u*>(pin);
+      {
+        const v4u w = __builtin_nontemporal_load(base + i);
+        const int sb = sin[g];
+        bad = sb == 255;
+        for (int d = 0; d < 4; ++d) {
+          for (int k = 0; k < 4; ++k) {
+            acc[4 * d + k] =
+                ldexpf(e4m3_to_f32((u8)(w[d] >> (8 * k))), sb - 127);
+          }
+        }
+      }
+      for (long long r = 1; r < nranks; ++r) {
+        const v4u w = __builtin_nontemporal_load(base + r * total + i);
+        const int sb = sin[r * n + g];
+        bad = bad || sb == 255;
+        for (int d = 0; d < 4; ++d) {
+          for (int k = 0; k < 4; ++k) {
+            acc[4 * d + k] +=
+                ldexpf(e4m3_to_f32((u8)(w[d] >> (8 * k))), sb - 127);
+          }
+        }
+      }
+    } else {
+      for (int k = 0; k < 16; ++k) acc[k] = 0.0f;
+    }
+    unsigned a = bad ? kInfBits : amax_bits_of(acc);
+    const unsigned o = (unsigned)__shfl_xor((int)a, 1);
+    a = o > a ? o : a;
+    int E;
+    const int sb = mx8_scale_byte(a, &E);
+    if (act) {
+      v4u w;
+      for (int d = 0; d < 4; ++d) {
+        w[d] = sb == 255 ? 0u
+                         : quant4(acc[4 * d], acc[4 * d + 1], acc[4 * d + 2],
+                                  acc[4 * d + 3], E);
+      }
+      __builtin_nontemporal_store(w, reinterpret_cast<v4u*>(pout) + i);
+    }
+    store_scales<2>(sout, i0 >> 1, n, sb, lane);
+  }
+}
+
+__global__ __launch_bounds__(256) void mx8_reduce_kernel_scalar(
+    const u8* __restrict__ pin, const u8* __restrict__ sin,
+    u8* __restrict__ pout, u8* __restrict__ sout, long long n,
+    long long nranks) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < n;
+       g += stride) {
+    float acc[32];
+    bool bad;
+    {
+      const int sb = sin[g];
+      bad = sb == 255;
+      for (int k = 0; k < 32; ++k) {
+        acc[k] = ldexpf(e4m3_to_f32(pin[g * 32 + k]), sb - 127);
+      }
+    }
+    for (long long r = 1; r < nranks; ++r) {
+      const int sb = sin[r * n + g];
+      bad = bad || sb == 255;
+      const u8* p = pin + (r * n + g) * 32;
+      for (int k = 0; k < 32; ++k) {
+        acc[k] += ldexpf(e4m3_to_f32(p[k]), sb - 127);
+      }
+    }
+    if (bad) acc[0] = __uint_as_float(kQNaNBits);
+    encode_group_scalar(acc, pout + g * 32, sout + g);
+  }
+}
+
+// ---- dequantize ---------------------------------------------------------
+
+template <int K>
+__global__ __launch_bounds__(256) void mx8_dequantize_kernel(
+    const u8* __restrict__ pay, const u8* __restrict__ sc,
+    void* __restrict__ out, long long nfull, long long N) {
+  using T = typename Elem<K>::type;
+  constexpr int LPG = K == kF32 ? 8 : 4;
+  constexpr int EPL = 32 / LPG;
+  const long long total = nfull * LPG;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+       i < total; i += stride) {
+    const int sb = sc[i / LPG];
+    unsigned w[EPL / 4];
+    if constexpr (K == kF32) {
+      w[0] = __builtin_nontemporal_load(
+          reinterpret_cast<const unsigned*>(pay) + i);
+    } else {
+      const v2u t =
+          __builtin_nontemporal_load(reinterpret_cast<const v2u*>(pay) + i);
+      w[0] = t[0];
+      w[EPL / 4 - 1] = t[1];
+    }
+    float x[EPL];
+    for (int d = 0; d < EPL / 4; ++d) {
+      for (int k = 0; k < 4; ++k) {
+        x[4 * d + k] = mx8_dequant((u8)(w[d] >> (8 * k)), sb);
+      }
+    }
+    __builtin_nontemporal_store(pack16<K, EPL>(x),
+                                reinterpret_cast<v4u*>(out) + i);
+  }
+  // partial last group: exactly N - 32*nfull elements, nothing past N
+  const int tail = (int)(N - nfull * 32);
+  if (tail > 0 && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+    dequant_group_scalar<K>(pay + nfull * 32, sc[nfull], tail,
+                            reinterpret_cast<T*>(out) + nfull * 32);
+  }
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void mx8_dequantize_kernel_scalar(
+    const u8* __restrict__ pay, const u8* __restrict__ sc,
+    void* __restrict__ out, long long G, long long N) {
+  using T = typename Elem<K>::type;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < G;
+       g += stride) {
+    const long long left = N - g * 32;
+    dequant_group_scalar<K>(pay + g * 32, sc[g], left < 32 ? (int)left : 32,
+                            reinterpret_cast<T*>(out) + g * 32);
+  }
+}
+
+inline unsigned grid_for(long long work) {
+  long long blocks = (work + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  if (blocks < 1) blocks = 1;
+  return (unsigned)blocks;
+}
+
+inline bool aligned(const void* p, uintptr_t a) {
+  return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0;
+}
+
+template <int K>
+void launch_quantize_t(const void* in, void* pay, void* sc, int64_t N,
+                       hipStream_t stream) {
+  constexpr int LPG = K == kF32 ? 8 : 4;
+  const long long G = (N + 31) / 32;
+  const long long nfull = N / 32;
+  if (aligned(in, 16) && aligned(pay, 32 / LPG)) {
+    hipLaunchKernelGGL((mx8_quantize_kernel<K>), dim3(grid_for(nfull * LPG)),
+                       dim3(256), 0, stream, in, static_cast<u8*>(pay),
+                       static_cast<u8*>(sc), nfull, (long long)N);
+  } else {
+    hipLaunchKernelGGL((mx8_quantize_kernel_scalar<K>), dim3(grid_for(G)),
+                       dim3(256), 0, stream, in, static_cast<u8*>(pay),
+                       static_cast<u8*>(sc), G, (long long)N);
+  }
+}
+
+template <int K>
+void launch_dequantize_t(const void* pay, const void* sc, void* out, int64_t N,
+                         hipStream_t stream) {
+  constexpr int LPG = K == kF32 ? 8 : 4;
+  const long long G = (N + 31) / 32;
+  const long long nfull = N / 32;
+  if (aligned(out, 16) && aligned(pay, 32 / LPG)) {
+    hipLaunchKernelGGL((mx8_dequantize_kernel<K>),
+                       dim3(grid_for(nfull * LPG)), dim3(256), 0, stream,
+                       static_cast<const u8*>(pay),
+                       static_cast<const u8*>(sc), out, nfull, (long long)N);
+  } else {
+    hipLaunchKernelGGL((mx8_dequantize_kernel_scalar<K>), dim3(grid_for(G)),
+                       dim3(256), 0, stream, static_cast<const u8*>(pay),
+                       static_cast<const u8*>(sc), out, G, (long long)N);
+  }
+}
+
+} // namespace
+
+void launch_mx8_quantize(const void* in, void* payload, void* scales,
+                         int64_t n_elems, int dtype, hipStream_t stream) {
+  if (n_elems <= 0) return;
+  switch (dtype) {
+    case 0: launch_quantize_t<kF32>(in, payload, scales, n_elems, stream); break;
+    case 1: launch_quantize_t<kBF16>(in, payload, scales, n_elems, stream); break;
+    default: launch_quantize_t<kF16>(in, payload, scales, n_elems, stream); break;
+  }
+}
+
+void launch_mx8_reduce(const void* payload_in, const void* scales_in,
+                       void* payload_out, void* scales_out, int64_t n_groups,
+                       int nranks, hipStream_t stream) {
+  if (n_groups <= 0) return;
+  const u8* pin = static_cast<const u8*>(payload_in);
+  const u8* sin = static_cast<const u8*>(scales_in);
+  u8* pout = static_cast<u8*>(payload_out);
+  u8* sout = static_cast<u8*>(scales_out);
+  if (aligned(pin, 16) && aligned(pout, 16)) {
+    hipLaunchKernelGGL(mx8_reduce_kernel, dim3(grid_for(n_groups * 2)),
+                       dim3(256), 0, stream, pin, sin, pout, sout,
+                       (long long)n_groups, (long long)nranks);
+  } else {
+    hipLaunchKernelGGL(mx8_reduce_kernel_scalar, dim3(grid_for(n_groups)),
+                       dim3(256), 0, stream, pin, sin, pout, sout,
+                       (long long)n_groups, (long long)nranks);
+  }
+}
+
+void launch_mx8_dequantize(const void* payload, const void* scales, void* out,
+                           int64_t n_elems, int dtype, hipStream_t stream) {
+  if (n_elems <= 0) return;
+  switch (dtype) {
+    case 0: launch_dequantize_t<kF32>(payload, scales, out, n_elems, stream); break;
+    case 1: launch_dequantize_t<kBF16>(payload, scales, out, n_elems, stream); break;
+    default: launch_dequantize_t<kF16>(payload, scales, out, n_elems, stream); break;
+  }
+}
+
+} // namespace m4a

@@ -661,6 +661,191 @@ Tensor allreduce_lowered(Transport& tr, const Tensor& in, int64_t op) {
   return red.to(in.scalar_type());
 }
 
+// ----------------------- mxfp8 compressed allreduce -----------------------
+//
+// Codec (normative; the gfx950 kernels in csrc/mx8_kernels.hip match this
+// torch composite byte for byte): groups of 32 consecutive elements of the
+// flat tensor, each 32 OCP e4m3fn payload bytes + one E8M0 scale byte.
+//   quantize : amax over |x| in fp32. Non-finite group -> scale 255, zero
+//              payload. amax == 0 -> E = 0. Else amax = m*2^k (frexp,
+//              m in [0.5,1)): E = k-9 if m <= 0.875 else k-8, clamped to
+//              [-127,127] — the smallest E with amax*2^-E <= 448. Scale
+//              byte E+127; payload = RNE(x * 2^-E) (exact scaling, never
+//              saturates).
+//   dequant  : fp32(byte) * 2^E (exact); scale 255 -> NaN group.
+//   reduce   : ((d_0 + d_1) + ...) in fp32 in rank order on dequantized
+//              values, then quantize. A 255 input or non-finite sum gives a
+//              255 group (NaN propagation does this in the composite).
+
+// 2^e as fp32 for int32 e in [-127,127], built from bits (2^-127 is the
+// subnormal 0x00400000) so no transcendental is involved.
+Tensor mx8_pow2(const Tensor& e) {
+  auto bits = at::where(e.ge(-126), (e + 127) * (1 << 23),
+                        at::full_like(e, 0x00400000));
+  return bits.to(at::kInt).contiguous().view(at::kFloat);
+}
+
+// xg: [G, 32] fp32 -> (payload [G, 32] u8, scales [G] u8)
+std::pair<Tensor, Tensor> mx8_quantize_groups(const Tensor& xg) {
+  auto finite = at::isfinite(xg).all(1);
+  auto amax = xg.abs().amax(1).masked_fill(finite.logical_not(), 0);
+  auto mk = at::frexp(amax);
+  auto m = std::get<0>(mk);
+  auto k = std::get<1>(mk).to(at::kInt);
+  auto E = k - at::where(m.le(0.875), at::full_like(k, 9), at::full_like(k, 8));
+  E = at::where(amax.eq(0), at::zeros_like(E), E).clamp(-127, 127);
+  auto scaled = xg * mx8_pow2(-E).unsqueeze(1);
+  auto pay = scaled.to(at::kFloat8_e4m3fn).view(at::kByte);
+  pay = at::where(finite.unsqueeze(1), pay, at::zeros_like(pay));
+  auto sc = at::where(finite, E + 127, at::full_like(E, 255)).to(at::kByte);
+  return {pay.contiguous(), sc.contiguous()};
+}
+
+// payload [G, 32] u8, scales [G] u8 -> [G, 32] fp32
+Tensor mx8_dequantize_groups(const Tensor& pay, const Tensor& sc) {
+  auto v = pay.contiguous().view(at::kFloat8_e4m3fn).to(at::kFloat);
+  auto E = (sc.to(at::kInt) - 127).clamp(-127, 127);
+  auto d = v * mx8_pow2(E).unsqueeze(1);
+  return at::where(sc.eq(255).unsqueeze(1),
+                   at::full_like(d, std::numeric_limits<float>::quiet_NaN()),
+                   d);
+}
+
+int mx8_dtype_code(at::ScalarType t) {
+  switch (t) {
+    case at::kFloat: return 0;
+    case at::kBFloat16: return 1;
+    case at::kHalf: return 2;
+    default:
+      TORCH_CHECK(false, "mpi4torch_amd: mxfp8 compression supports "
+                  "float32, bfloat16 and float16 tensors, got ", t);
+  }
+}
+
+// flat contiguous x -> (payload [G*32] u8, scales [G] u8), G = ceil(N/32)
+std::pair<Tensor, Tensor> mx8_quantize(const Tensor& x) {
+  const int dt = mx8_dtype_code(x.scalar_type());
+  const int64_t N = x.numel();
+  const int64_t G = (N + 31) / 32;
+  auto bopts = x.options().dtype(at::kByte);
+  if (x.is_cuda()) {
+    auto pay = at::empty({G * 32}, bopts);
+    auto sc = at::empty({G}, bopts);
+    launch_mx8_quantize(x.data_ptr(), pay.data_ptr(), sc.data_ptr(), N, dt,
+                        current_gpu_stream(x));
+    return {pay, sc};
+  }
+  auto padded = at::zeros({G * 32}, x.options().dtype(at::kFloat));
+  padded.narrow(0, 0, N).copy_(x.view({-1}));
+  auto ps = mx8_quantize_groups(padded.view({G, 32}));
+  return {ps.first.view({-1}), ps.second};
+}
+
+// P copies: pin [P * n*32], sin [P * n] -> pout [n*32], sout [n] (views ok)
+void mx8_reduce(const Tensor& pin, const Tensor& sin, Tensor& pout,
+                Tensor& sout, int64_t n, int P) {
+  if (n == 0) return;
+  if (pin.is_cuda()) {
+    launch_mx8_reduce(pin.data_ptr(), sin.data_ptr(), pout.data_ptr(),
+                      sout.data_ptr(), n, P, current_gpu_stream(pin));
+    return;
+  }
+  auto pv = pin.view({P, n, 32});
+  auto sv = sin.view({P, n});
+  auto acc = mx8_dequantize_groups(pv[0], sv[0]);
+  for (int r = 1; r < P; ++r) {
+    acc = acc + mx8_dequantize_groups(pv[r], sv[r]);
+  }
+  auto ps = mx8_quantize_groups(acc);
+  pout.copy_(ps.first.view({-1}));
+  sout.copy_(ps.second);
+}
+
+// payload [G*32], scales [G] -> flat [numel] of `dtype`
+Tensor mx8_dequantize(const Tensor& pay, const Tensor& sc, int64_t numel,
+                      at::ScalarType dtype) {
+  const int dt = mx8_dtype_code(dtype);
+  if (pay.is_cuda()) {
+    auto out = at::empty({numel}, pay.options().dtype(dtype));
+    launch_mx8_dequantize(pay.data_ptr(), sc.data_ptr(), out.data_ptr(),
+                          numel, dt, current_gpu_stream(pay));
+    return out;
+  }
+  const int64_t G = sc.numel();
+  auto d = mx8_dequantize_groups(pay.view({G, 32}), sc).view({-1});
+  return d.narrow(0, 0, numel).to(dtype);
+}
+
+// The mxfp8 sibling of hierarchical_allreduce: quantize once, exchange each
+// rank's copy of group-block j to rank j (payload and scales as two
+// contiguous pieces per peer in ONE grouped call), fused
+// dequantize-sum-requantize of the owned block, allgather payload + scales
+// in place, dequantize. Values are quantized exactly twice at any P; every
+// rank decodes the same bytes, so results are identical across ranks.
+// Staging is ~33/32 * numel bytes twice (quantized input, P copies of the
+// owned block), never P * numel.
+Tensor mx8_allreduce(Transport& tr, const Tensor& in) {
+  const int P = tr.size();
+  const int me = tr.rank();
+  const int64_t N = in.numel();
+  const int64_t G = (N + 31) / 32;
+  std::vector<int64_t> counts(P);
+  for (int p = 0; p < P; ++p) counts[p] = G / P + (p < G % P ? 1 : 0);
+  auto displs = prefix_displs(counts);
+  auto nz_narrow = [](const Tensor& t, int64_t off, int64_t len) {
+    return len > 0 ? t.narrow(0, off, len) : t.narrow(0, 0, 0);
+  };
+  auto q = mx8_quantize(in.view({-1}));
+  const int64_t cm = counts[me];
+  // phase 1: one grouped exchange carrying payload and scales
+  auto bopts = in.options().dtype(at::kByte);
+  auto stg_pay = at::empty({(int64_t)P * cm * 32}, bopts);
+  auto stg_sc = at::empty({(int64_t)P * cm}, bopts);
+  std::vector<Tensor> sends(2 * P), recvs(2 * P);
+  std::vector<int> peers(2 * P);
+  for (int p = 0; p < P; ++p) {
+    sends[2 * p] = nz_narrow(q.first, displs[p] * 32, counts[p] * 32);
+    sends[2 * p + 1] = nz_narrow(q.second, displs[p], counts[p]);
+    recvs[2 * p] = nz_narrow(stg_pay, (int64_t)p * cm * 32, cm * 32);
+    recvs[2 * p + 1] = nz_narrow(stg_sc, (int64_t)p * cm, cm);
+    peers[2 * p] = peers[2 * p + 1] = p;
+  }
+  tr.exchange(sends, peers, recvs, peers);
+  // phase 2: fused reduce of the P copies of the owned groups
+  auto out_pay = at::empty({G * 32}, bopts);
+  auto out_sc = at::empty({G}, bopts);
+  auto my_pay = nz_narrow(out_pay, displs[me] * 32, cm * 32);
+  auto my_sc = nz_narrow(out_sc, displs[me], cm);
+  mx8_reduce(stg_pay, stg_sc, my_pay, my_sc, cm, P);
+  // phase 3: allgather payload + scales (equal counts on GPU: RCCL, in
+  // place; otherwise grouped p2p — same split as hierarchical_allreduce)
+  if (G % P == 0 && tr.is_gpu()) {
+    tr.allgather_equal(my_pay, out_pay);
+    tr.allgather_equal(my_sc, out_sc);
+  } else {
+    std::vector<Tensor> s2, r2;
+    std::vector<int> sp, rp;
+    for (int p = 0; p < P; ++p) {
+      if (p == me) continue;
+      if (cm > 0) {
+        s2.push_back(my_pay);
+        sp.push_back(p);
+        s2.push_back(my_sc);
+        sp.push_back(p);
+      }
+      if (counts[p] > 0) {
+        r2.push_back(out_pay.narrow(0, displs[p] * 32, counts[p] * 32));
+        rp.push_back(p);
+        r2.push_back(out_sc.narrow(0, displs[p], counts[p]));
+        rp.push_back(p);
+      }
+    }
+    tr.exchange(s2, sp, r2, rp);
+  }
+  return mx8_dequantize(out_pay, out_sc, N, in.scalar_type())
+      .view(in.sizes());
+}
+
 // ------------------------- autograd node base -----------------------------
 
 struct M4ANode : public Node {
@@ -762,6 +947,61 @@ Tensor Communicator::Allreduce(const Tensor& input, int64_t op) {
     auto& tr = tr_for(in);
     debug_check_collective(group_name_, "Allreduce", in, {op});
     return stager.from_comm(allreduce_lowered(tr, in, op));
+  }();
+  attach_history(result, grad_fn);
+  return result;
+}
+
+// ---------------------------------------------------------------------------
+// AllreduceCompressed (MI355X extension; not in the reference API)
+// ---------------------------------------------------------------------------
+
+namespace {
+struct AllreduceCompressedBackward : public M4ANode {
+  std::string name() const override {
+    return "M4AAllreduceCompressedBackward";
+  }
+  variable_list apply(variable_list&& grads) override {
+    variable_list out(1);
+    if (should_compute_output(0)) {
+      // treated as the self-adjoint sum; quantization is straight-through,
+      // and the gradient itself travels compressed
+      out[0] = comm->AllreduceCompressed(grads[0], kSum);
+    }
+    return out;
+  }
+};
+} // namespace
+
+Tensor Communicator::AllreduceCompressed(const Tensor& input, int64_t op) {
+  TORCH_CHECK(op == kSum,
+              "mpi4torch_amd: AllreduceCompressed supports MPI_SUM only "
+              "(got ", red_op_name(op), ")");
+  TORCH_CHECK(input.scalar_type() == at::kFloat ||
+                  input.scalar_type() == at::kBFloat16 ||
+                  input.scalar_type() == at::kHalf,
+              "mpi4torch_amd: AllreduceCompressed supports float32, "
+              "bfloat16 and float16 tensors, got ", input.scalar_type());
+  std::shared_ptr<M4ANode> grad_fn;
+  if (torch::autograd::compute_requires_grad(input)) {
+    grad_fn = make_node<AllreduceCompressedBackward>(
+        c10::intrusive_ptr<Communicator>::unsafe_reclaim_from_nonowning(this));
+    grad_fn->set_next_edges(torch::autograd::collect_next_edges(input));
+  }
+  auto result = [&]() {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    DeviceStager stager(input);
+    auto in = stager.to_comm(input).contiguous().variable_data();
+    auto& tr = tr_for(in);
+    debug_check_collective(group_name_, "AllreduceCompressed", in, {op});
+    if (in.numel() == 0) return stager.from_comm(in.clone());
+    // World of one: nothing crosses a wire, so nothing is compressed — the
+    // result is an exact clone. force_full_path (GPU) runs the whole
+    // pipeline instead: self-exchange, all three kernels, allgather.
+    if (tr.size() == 1 && !(config().force_full_path && in.is_cuda())) {
+      return stager.from_comm(fast_clone(in));
+    }
+    return stager.from_comm(mx8_allreduce(tr, in));
   }();
   attach_history(result, grad_fn);
   return result;
@@ -2157,6 +2397,60 @@ Tensor debug_fp8_reduce(const Tensor& stacked, int64_t op) {
                     (int)op, in.scalar_type() == at::kFloat8_e5m2,
                     current_gpu_stream(in));
   return out;
+}
+
+std::tuple<Tensor, Tensor> debug_mx8_quantize(const Tensor& x) {
+  auto ps = mx8_quantize(x.contiguous().view({-1}));
+  return std::make_tuple(ps.first, ps.second);
+}
+
+std::tuple<Tensor, Tensor> debug_mx8_reduce(const Tensor& payload,
+                                            const Tensor& scales) {
+  TORCH_CHECK(payload.dim() == 2 && scales.dim() == 2 &&
+                  payload.scalar_type() == at::kByte &&
+                  scales.scalar_type() == at::kByte &&
+                  payload.size(0) == scales.size(0) &&
+                  payload.size(1) == scales.size(1) * 32,
+              "debug_mx8_reduce expects uint8 payload [P, G*32] and "
+              "scales [P, G]");
+  auto pin = payload.contiguous();
+  auto sin = scales.contiguous();
+  const int64_t P = sin.size(0), n = sin.size(1);
+  TORCH_CHECK(P >= 1);
+  auto pout = at::empty({n * 32}, pin.options());
+  auto sout = at::empty({n}, sin.options());
+  mx8_reduce(pin.view({-1}), sin.view({-1}), pout, sout, n, (int)P);
+  return std::make_tuple(pout, sout);
+}
+
+Tensor debug_mx8_dequantize(const Tensor& payload, const Tensor& scales,
+                            int64_t numel, at::ScalarType dtype,
+                            const c10::optional<Tensor>& out) {
+  TORCH_CHECK(payload.scalar_type() == at::kByte &&
+                  scales.scalar_type() == at::kByte &&
+                  payload.numel() == scales.numel() * 32 &&
+                  numel >= 0 && numel <= payload.numel() &&
+                  (numel + 31) / 32 == scales.numel(),
+              "debug_mx8_dequantize expects uint8 payload [G*32], scales "
+              "[G] and numel in (32*(G-1), 32*G]");
+  auto pay = payload.contiguous().view({-1});
+  auto sc = scales.contiguous().view({-1});
+  if (!out.has_value()) return mx8_dequantize(pay, sc, numel, dtype);
+  // write the first `numel` elements of a caller buffer (canary tests)
+  const Tensor& o = *out;
+  TORCH_CHECK(o.dim() == 1 && o.is_contiguous() && o.numel() >= numel &&
+                  o.scalar_type() == dtype && o.device() == pay.device(),
+              "debug_mx8_dequantize: out must be a flat contiguous tensor "
+              "of the requested dtype with at least numel elements");
+  auto head = o.narrow(0, 0, numel);
+  if (pay.is_cuda()) {
+    launch_mx8_dequantize(pay.data_ptr(), sc.data_ptr(), head.data_ptr(),
+                          numel, mx8_dtype_code(dtype),
+                          current_gpu_stream(pay));
+  } else {
+    head.copy_(mx8_dequantize(pay, sc, numel, dtype));
+  }
+  return head;
 }
 
 Tensor debug_pairloc_reduce(const Tensor& stacked, int64_t op) {

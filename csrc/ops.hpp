@@ -14,6 +14,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <tuple>
 #include <vector>
 
 namespace m4a {
@@ -28,6 +29,14 @@ struct Communicator : torch::CustomClassHolder {
 
   // Collectives (autograd-transparent; adjoints per SURVEY.md §3.3).
   at::Tensor Allreduce(const at::Tensor& input, int64_t op);
+  // Block-scaled fp8 compressed allreduce (MI355X extension): the tensor
+  // travels as mxfp8 (32 e4m3 bytes + one shared-exponent byte per 32
+  // elements, 33/32 byte per element) through the hierarchical exchange +
+  // fused gfx950 reduce kernel; values are quantized exactly twice at any
+  // world size. MPI_SUM only; float32/bfloat16/float16 only. Backward:
+  // AllreduceCompressed of the gradient (self-adjoint sum, straight-through
+  // quantization). A world of one returns an exact clone.
+  at::Tensor AllreduceCompressed(const at::Tensor& input, int64_t op);
   at::Tensor Bcast_(const at::Tensor& input, int64_t root);
   at::Tensor Reduce_(const at::Tensor& input, int64_t op, int64_t root);
   at::Tensor Gather(const at::Tensor& input, int64_t gatheraxis, int64_t root);
@@ -120,6 +129,16 @@ at::Tensor debug_pack_roundtrip(const at::Tensor& input, int64_t axis,
                                 std::vector<int64_t> counts);
 at::Tensor debug_bitwise_reduce(const at::Tensor& stacked, int64_t op);
 at::Tensor debug_fp8_reduce(const at::Tensor& stacked, int64_t op);
+// mxfp8 codec entry points: the torch composite for CPU tensors, the gfx950
+// kernels for GPU tensors (tests compare the two byte for byte).
+std::tuple<at::Tensor, at::Tensor> debug_mx8_quantize(const at::Tensor& x);
+// payload [P, G*32], scales [P, G] -> (payload [G*32], scales [G])
+std::tuple<at::Tensor, at::Tensor> debug_mx8_reduce(const at::Tensor& payload,
+                                                    const at::Tensor& scales);
+at::Tensor debug_mx8_dequantize(const at::Tensor& payload,
+                                const at::Tensor& scales, int64_t numel,
+                                at::ScalarType dtype,
+                                const c10::optional<at::Tensor>& out);
 // stacked: [nranks, ..., 2] (value, location) pairs; op: 0=minloc 1=maxloc
 at::Tensor debug_pairloc_reduce(const at::Tensor& stacked, int64_t op);
 

@@ -151,6 +151,29 @@ class MPI_Communicator:
         """
         return self._comm.Allreduce(tensor, op)
 
+    def AllreduceCompressed(self, tensor: torch.Tensor,
+                            op: int = 2) -> torch.Tensor:
+        """Sum-Allreduce that travels as block-scaled fp8 (MI355X extension).
+
+        The tensor (float32, bfloat16 or float16) is quantized to mxfp8 —
+        groups of 32 consecutive elements, OCP e4m3 payload plus one shared
+        power-of-two scale byte, 33/32 byte per element on the wire — then
+        reduced by the hierarchical exchange + fused gfx950 kernel and
+        dequantized back to the input dtype. Values are quantized exactly
+        twice (input, and after the fp32 sum) at any world size, and the
+        result is bit-identical on every rank. A group holding inf/NaN
+        comes back as NaN, so overflow checks still fire. ``op`` must be
+        MPI_SUM (the default; the literal 2 because module globals are not
+        visible inside a TorchScript class body).
+
+        A world of one returns an exact clone: nothing crosses a wire, so
+        nothing is compressed.
+
+        Backward: AllreduceCompressed of the gradient. The op is treated as
+        the self-adjoint sum; quantization is straight-through.
+        """
+        return self._comm.AllreduceCompressed(tensor, op)
+
     def Bcast_(self, tensor: torch.Tensor, root: int) -> torch.Tensor:
         """Broadcast from ``root`` (in place). Backward: Reduce_ to root."""
         return self._comm.Bcast_(tensor, root)

@@ -19,6 +19,13 @@ def allreduce(tensor: torch.Tensor, op: Optional[int] = None, comm=None):
     return _comm(comm).Allreduce(tensor, _m.MPI_SUM if op is None else op)
 
 
+def allreduce_compressed(tensor: torch.Tensor, op: Optional[int] = None,
+                         comm=None):
+    """Sum-Allreduce over an mxfp8 wire (33/32 byte per element)."""
+    return _comm(comm).AllreduceCompressed(
+        tensor, _m.MPI_SUM if op is None else op)
+
+
 def bcast_(tensor: torch.Tensor, root: int = 0, comm=None):
     return _comm(comm).Bcast_(tensor, root)
 

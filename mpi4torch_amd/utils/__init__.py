@@ -1,4 +1,5 @@
-from .timing import CollectiveTimer, algbw_gbps, busbw_gbps
+from .timing import (CollectiveTimer, algbw_gbps, busbw_gbps,
+                     mxfp8_wire_bytes)
 from .tracing import trace, TracedCommunicator, TraceRecord
 from .checkpoint import (save_checkpoint, load_checkpoint,
                          save_sharded_checkpoint, load_sharded_checkpoint)
@@ -8,6 +9,7 @@ __all__ = [
     "CollectiveTimer",
     "algbw_gbps",
     "busbw_gbps",
+    "mxfp8_wire_bytes",
     "trace",
     "TracedCommunicator",
     "TraceRecord",

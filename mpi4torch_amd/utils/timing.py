@@ -27,6 +27,14 @@ def busbw_gbps(nbytes: int, seconds: float, world: int, op: str = "allreduce") -
     return a
 
 
+def mxfp8_wire_bytes(numel: int) -> int:
+    """Bytes AllreduceCompressed puts on the wire for ``numel`` elements:
+    32 e4m3 payload bytes plus one shared-exponent byte per group of 32
+    (the partial last group is padded), i.e. 33/32 byte per element —
+    1.94x fewer than bf16, 3.88x fewer than fp32."""
+    return 33 * ((numel + 31) // 32)
+
+
 class CollectiveTimer:
     """Times GPU regions with CUDA/HIP events (no host sync until query)."""
 

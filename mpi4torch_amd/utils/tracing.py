@@ -92,6 +92,11 @@ class TracedCommunicator:
         return self._record("Allreduce", tensor,
                             lambda: self._comm.Allreduce(tensor, op))
 
+    def AllreduceCompressed(self, tensor, op=2):
+        return self._record(
+            "AllreduceCompressed", tensor,
+            lambda: self._comm.AllreduceCompressed(tensor, op))
+
     def Bcast_(self, tensor, root):
         return self._record("Bcast_", tensor,
                             lambda: self._comm.Bcast_(tensor, root))

@@ -19,6 +19,7 @@ OUT = os.path.join(REPO, "mpi4torch_amd", "_C.so")
 
 SOURCES = [
     "kernels.hip",
+    "mx8_kernels.hip",
     "transport.cpp",
     "ops.cpp",
     "extension.cpp",

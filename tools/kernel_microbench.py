@@ -4,7 +4,12 @@ local-reduce and marshaling kernels vs the ~8 TB/s HBM3E peak.
 
 Each kernel moves (nranks*N reads + N writes) or (N reads + N writes) —
 reported GB/s counts actual bytes touched. Run on an MI355X box:
-    python tools/kernel_microbench.py
+    python tools/kernel_microbench.py            # everything
+    python tools/kernel_microbench.py --mx8      # only the mxfp8 codec section
+
+The mxfp8 section times the three codec kernels and, in the same run and
+alternating with it, the sibling fp8_reduce kernel at the same P and n, so
+the ratio between the two is not a comparison across runs.
 """
 
 import os
@@ -47,6 +52,81 @@ def report(name, ms, nbytes):
 P = 8
 N = 64 << 20  # 64M elements per chunk
 
+
+def mx8_section(repeats=5):
+    """mxfp8 codec kernels. Bytes are what each kernel actually moves:
+    quantize N*esize in + 33N/32 out, reduce P*33n/32 in + 33n/32 out,
+    dequantize the mirror of quantize. Every launch's working set is larger
+    than the 256 MiB Infinity Cache (the same buffers are reused across
+    iterations): quantize/dequantize run at 256Mi elements (>= 776 MiB per
+    launch), the reduce at P x 64 MiB of payload (594 MiB)."""
+    C = m._C
+    NQ = 256 << 20
+    med = lambda v: sorted(v)[len(v) // 2]
+
+    def line(name, times, nbytes):
+        t = med(times)
+        print(f"{name:34s} {t*1e3:9.1f} us  {nbytes/t/1e6:8.1f} GB/s  "
+              f"(min {min(times)*1e3:.1f} max {max(times)*1e3:.1f} us, "
+              f"{len(times)} repeats)", flush=True)
+        return t
+
+    for dtype, tag in ((torch.float32, "fp32"), (torch.bfloat16, "bf16"),
+                       (torch.float16, "fp16")):
+        x = torch.randn(NQ, device="cuda")
+        x.view(-1, 32).mul_(torch.rand(NQ // 32, 1, device="cuda"))
+        x = x.to(dtype)
+        es = x.element_size()
+        wire = 33 * NQ // 32
+        tq = [timeit(lambda: C._mx8_quantize(x)) for _ in range(repeats)]
+        line(f"mx8_quantize {tag} N={NQ>>20}Mi", tq, NQ * es + wire)
+        pay, sc = C._mx8_quantize(x)
+        td = [timeit(lambda: C._mx8_dequantize(pay, sc, NQ, dtype))
+              for _ in range(repeats)]
+        line(f"mx8_dequantize {tag} N={NQ>>20}Mi", td, NQ * es + wire)
+        del x, pay, sc
+
+    # reduce vs its sibling, alternating, same P and n
+    wire = 33 * N // 32
+    src = torch.randn(P, N, device="cuda") * 0.2
+    stk8 = src.to(torch.float8_e4m3fn)
+    qs = [C._mx8_quantize(src[r]) for r in range(P)]
+    pay = torch.stack([q[0] for q in qs])
+    sc = torch.stack([q[1] for q in qs])
+    del src, qs
+    t_new, t_sib = [], []
+    for _ in range(repeats):
+        t_sib.append(timeit(lambda: C._fp8_reduce(stk8, 0)))
+        t_new.append(timeit(lambda: C._mx8_reduce(pay, sc)))
+    a = line(f"fp8_reduce (sibling) P={P} n={N>>25}Mi grp", t_sib,
+             (P + 1) * N)
+    b = line(f"mx8_reduce P={P} n={N>>25}Mi groups", t_new, (P + 1) * wire)
+    spread = (max(t_sib) - min(t_sib)) / med(t_sib)
+    print(f"mx8_reduce / fp8_reduce time ratio {b/a:.3f} "
+          f"(sibling spread {spread*100:.1f}% of its median; the mx8 kernel "
+          f"moves 33/32 = 1.031x the bytes)", flush=True)
+
+    # informational: codec overhead of the full pipeline at world size 1
+    # (no wire at this size: self-exchange + three kernels + allgather)
+    t = torch.randn(128 << 20, device="cuda").to(torch.bfloat16)  # 256 MiB
+    comm = m.COMM_WORLD
+    C.force_full_path(True)
+    try:
+        tc = [timeit(lambda: comm.AllreduceCompressed(t, m.MPI_SUM), iters=10)
+              for _ in range(3)]
+        ta = [timeit(lambda: comm.Allreduce(t, m.MPI_SUM), iters=10)
+              for _ in range(3)]
+    finally:
+        C.force_full_path(False)
+    line("w1 full-path AllreduceCompressed", tc, t.numel() * 2)
+    line("w1 full-path Allreduce (RCCL)", ta, t.numel() * 2)
+
+
+if "--mx8" in sys.argv:
+    mx8_section()
+    dist.destroy_process_group()
+    sys.exit(0)
+
 # fp8 local reduce: P chunks fp8 -> 1 chunk fp8, fp32 accumulation
 stk8 = (torch.randn(P, N, device="cuda") * 0.2).to(torch.float8_e4m3fn)
 ms = timeit(lambda: m._C._fp8_reduce(stk8, 0))
@@ -78,5 +158,8 @@ t = torch.randn(N, device="cuda")
 comm = m.COMM_WORLD
 ms = timeit(lambda: comm.Allreduce(t, m.MPI_SUM))
 report("w1 fast-path clone 64Mi fp32", ms, 2 * N * 4)
+del stk8, stki, stkp, x, t
+
+mx8_section()
 
 dist.destroy_process_group()
