@@ -96,6 +96,18 @@ struct Config {
   // can hide ~2*payload/5TB/s of marshaling — net-positive only when the
   // wire is the slow side (multi-GPU) and payloads are >= ~1 GiB/rank.
   int64_t pipeline_chunk_bytes = 256ll << 20;
+  // MPI4TORCH_AMD_ALLREDUCE=auto|native|rccl: which engine reduces the
+  // dtypes the transport's allreduce can carry.
+  //   auto   (default) a forced world of one (force_full_path) runs
+  //          native_allreduce, which at P = 1 is one bit-copy kernel;
+  //          P > 1 stays on ncclAllReduce (no multi-GPU measurement
+  //          supports a flip).
+  //   native bf16/fp16/fp32 arithmetic ops run native_allreduce at any P,
+  //          on the gloo transport too (tests); other dtypes stay on the
+  //          transport.
+  //   rccl   always the transport's allreduce, forced P = 1 included.
+  enum AllreduceEngine : int { kAllreduceAuto = 0, kAllreduceNative, kAllreduceRccl };
+  int allreduce_engine = kAllreduceAuto;
 };
 
 Config& config();

@@ -104,6 +104,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("_pack_roundtrip", &m4a::debug_pack_roundtrip);
   m.def("_bitwise_reduce", &m4a::debug_bitwise_reduce);
   m.def("_fp8_reduce", &m4a::debug_fp8_reduce);
+  m.def("_arith_reduce", &m4a::debug_arith_reduce);
   m.def("_pairloc_reduce", &m4a::debug_pairloc_reduce);
   m.def("_mx8_quantize", &m4a::debug_mx8_quantize);
   m.def("_mx8_reduce", &m4a::debug_mx8_reduce);

@@ -3,12 +3,13 @@
 // These kernels are the MI355X-native replacement for the CPU-side MPI
 // derived-datatype marshaling the reference uses for axis-aware collectives
 // (reference csrc/extension.cpp:556-577, 691-712, 839-861) and for the
-// reduction ops RCCL lacks. Four families: strided slab pack/unpack
+// reduction ops RCCL lacks. Five families: strided slab pack/unpack
 // between tensors and contiguous RCCL staging buffers; bitwise reduction
 // (MPI_BAND/BOR/BXOR); fused fp8 reduction with fp32 accumulation and a
-// single quantization; and the MINLOC/MAXLOC pair arg-reduce. The latter
-// three are the local tails of the hierarchical allreduce lowering
-// (csrc/ops.cpp hierarchical_allreduce).
+// single quantization; the MINLOC/MAXLOC pair arg-reduce; and the
+// bf16/fp16/fp32 arithmetic reduce. The middle three are the local tails
+// of the hierarchical allreduce lowering (csrc/ops.cpp
+// hierarchical_allreduce), the last one that of native_allreduce.
 //
 // Written directly for gfx950: 64-wide wavefronts, 256-thread workgroups,
 // 16-byte (dwordx4) vectorized global accesses, grids sized >> 256
@@ -510,6 +511,280 @@ void launch_fp8_reduce(const void* in, void* out, int64_t n_elems, int nranks,
       launch_fp8_reduce_t<Op, true>(in, out, n_elems, nranks, stream);
     } else {
       launch_fp8_reduce_t<Op, false>(in, out, n_elems, nranks, stream);
+    }
+  };
+  switch (op) {
+    case 0: dispatch(FAdd{}); break;
+    case 1: dispatch(FMul{}); break;
+    case 2: dispatch(FMin{}); break;
+    default: dispatch(FMax{}); break;
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Arithmetic reduce for the gradient dtypes (bf16/fp16/fp32): the local
+// tail of native_allreduce (csrc/ops.cpp). Unlike the kernels above it reads
+// its sources where they lie: the rank's own block straight from the input
+// tensor, the other nranks-1 copies from staging, combined in rank order.
+// 16-bit dtypes accumulate in fp32 and round once (RNE) at the end — a bf16
+// running sum would round to 8 significant bits at every step.
+//
+// Grid: one 16-byte vector per thread and one workgroup per 256 vectors, no
+// grid-stride cap. For the pure copy at 1 GiB that measured 6.6 TB/s against
+// 5.2 TB/s for the 4096-workgroup grid-stride form the kernels above use
+// (profiles/native_allreduce_n1.md); 2/4/8 vectors per thread were slower
+// than one at every grid size tried. The block-stride loop only exists so
+// grids beyond kMaxGrid stay legal.
+// ---------------------------------------------------------------------------
+
+namespace {
+
+constexpr long long kMaxGrid = 1ll << 30;
+
+struct TF32 {
+  using S = float;
+  static constexpr int E = 4;  // elements per 16-byte vector
+  __device__ static void unpack(v4u w, float* f) {
+    for (int d = 0; d < 4; ++d) f[d] = __uint_as_float(w[d]);
+  }
+  __device__ static v4u pack(const float* f) {
+    v4u o;
+    for (int d = 0; d < 4; ++d) o[d] = __float_as_uint(f[d]);
+    return o;
+  }
+  __device__ static float ld(const S* p) { return *p; }
+  __device__ static void st(S* p, float f) { *p = f; }
+};
+
+// fp32 -> bf16, round to nearest even, NaN -> canonical quiet NaN (the same
+// rule c10::BFloat16 applies, so torch casts are the bit-exact reference)
+__device__ inline unsigned int f32_to_bf16_bits(float f) {
+  const unsigned int u = __float_as_uint(f);
+  if (f != f) return 0x7FC0u;
+  return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+
+struct TBF16 {
+  using S = unsigned short;
+  static constexpr int E = 8;
+  __device__ static void unpack(v4u w, float* f) {
+    for (int d = 0; d < 4; ++d) {
+      f[2 * d] = __uint_as_float(w[d] << 16);
+      f[2 * d + 1] = __uint_as_float(w[d] & 0xFFFF0000u);
+    }
+  }
+  __device__ static v4u pack(const float* f) {
+    v4u o;
+    for (int d = 0; d < 4; ++d) {
+      o[d] = f32_to_bf16_bits(f[2 * d]) | (f32_to_bf16_bits(f[2 * d + 1]) << 16);
+    }
+    return o;
+  }
+  __device__ static float ld(const S* p) {
+    return __uint_as_float((unsigned int)*p << 16);
+  }
+  __device__ static void st(S* p, float f) { *p = (S)f32_to_bf16_bits(f); }
+};
+
+__device__ inline float f16_bits_to_f32(unsigned int b) {
+  return (float)__builtin_bit_cast(_Float16, (unsigned short)b);
+}
+__device__ inline unsigned int f32_to_f16_bits(float f) {
+  return __builtin_bit_cast(unsigned short, (_Float16)f);  // v_cvt, RNE
+}
+
+struct TF16 {
+  using S = unsigned short;
+  static constexpr int E = 8;
+  __device__ static void unpack(v4u w, float* f) {
+    for (int d = 0; d < 4; ++d) {
+      f[2 * d] = f16_bits_to_f32(w[d] & 0xFFFFu);
+      f[2 * d + 1] = f16_bits_to_f32(w[d] >> 16);
+    }
+  }
+  __device__ static v4u pack(const float* f) {
+    v4u o;
+    for (int d = 0; d < 4; ++d) {
+      o[d] = f32_to_f16_bits(f[2 * d]) | (f32_to_f16_bits(f[2 * d + 1]) << 16);
+    }
+    return o;
+  }
+  __device__ static float ld(const S* p) { return f16_bits_to_f32(*p); }
+  __device__ static void st(S* p, float f) { *p = (S)f32_to_f16_bits(f); }
+};
+
+// Source r of the reduction: the own block for r == me, else staging slot
+// r (r < me) or r-1 (r > me).
+__device__ inline const char* arith_src(const char* own, const char* staged,
+                                        long long stride_b, int me, int r) {
+  return r == me ? own : staged + (long long)(r - (r > me ? 1 : 0)) * stride_b;
+}
+
+template <typename T, typename Op>
+__device__ inline void arith_reduce_scalar_range(
+    const char* own, const char* staged, long long stride_b, int nranks,
+    int me, char* out, long long lo, long long hi, long long step) {
+  using S = typename T::S;
+  for (long long e = lo; e < hi; e += step) {
+    float acc = T::ld(
+        reinterpret_cast<const S*>(arith_src(own, staged, stride_b, me, 0)) + e);
+    for (int r = 1; r < nranks; ++r) {
+      acc = Op::apply(
+          acc, T::ld(reinterpret_cast<const S*>(
+                         arith_src(own, staged, stride_b, me, r)) + e));
+    }
+    T::st(reinterpret_cast<S*>(out) + e, acc);
+  }
+}
+
+// Work item i < nvec reduces vector i; item nvec (present only when
+// n_elems is not a multiple of the vector) reduces the tail elements.
+template <typename T, typename Op>
+__global__ __launch_bounds__(256) void arith_reduce_kernel(
+    const char* __restrict__ own, const char* __restrict__ staged,
+    long long stride_b, int nranks, int me, char* __restrict__ out,
+    long long nvec, long long n_elems) {
+  constexpr int E = T::E;
+  const long long items = nvec + (n_elems > nvec * E ? 1 : 0);
+  for (long long t = blockIdx.x; t * 256 < items; t += gridDim.x) {
+    const long long i = t * 256 + threadIdx.x;
+    if (i < nvec) {
+      float acc[E];
+      T::unpack(__builtin_nontemporal_load(
+                    reinterpret_cast<const v4u*>(
+                        arith_src(own, staged, stride_b, me, 0)) + i),
+                acc);
+      for (int r = 1; r < nranks; ++r) {
+        float x[E];
+        T::unpack(__builtin_nontemporal_load(
+                      reinterpret_cast<const v4u*>(
+                          arith_src(own, staged, stride_b, me, r)) + i),
+                  x);
+        for (int k = 0; k < E; ++k) acc[k] = Op::apply(acc[k], x[k]);
+      }
+      __builtin_nontemporal_store(T::pack(acc),
+                                  reinterpret_cast<v4u*>(out) + i);
+    } else if (i == nvec) {
+      arith_reduce_scalar_range<T, Op>(own, staged, stride_b, nranks, me, out,
+                                       nvec * E, n_elems, 1);
+    }
+  }
+}
+
+// general path: any alignment, one element per thread
+template <typename T, typename Op>
+__global__ __launch_bounds__(256) void arith_reduce_kernel_scalar(
+    const char* __restrict__ own, const char* __restrict__ staged,
+    long long stride_b, int nranks, int me, char* __restrict__ out,
+    long long n_elems) {
+  arith_reduce_scalar_range<T, Op>(
+      own, staged, stride_b, nranks, me, out,
+      (long long)blockIdx.x * blockDim.x + threadIdx.x, n_elems,
+      (long long)gridDim.x * blockDim.x);
+}
+
+// nranks == 1: the result is the input. Raw 16-byte moves, no float
+// conversion, so NaN payloads, -0.0 and subnormals pass bit for bit and the
+// kernel serves every dtype. Item nvec copies the tail bytes.
+__global__ __launch_bounds__(256) void arith_reduce_copy_kernel(
+    const char* __restrict__ src, char* __restrict__ dst, long long nvec,
+    long long nbytes) {
+  const long long items = nvec + (nbytes > nvec * 16 ? 1 : 0);
+  for (long long t = blockIdx.x; t * 256 < items; t += gridDim.x) {
+    const long long i = t * 256 + threadIdx.x;
+    if (i < nvec) {
+      __builtin_nontemporal_store(
+          __builtin_nontemporal_load(reinterpret_cast<const v4u*>(src) + i),
+          reinterpret_cast<v4u*>(dst) + i);
+    } else if (i == nvec) {
+      for (long long k = nvec * 16; k < nbytes; ++k) dst[k] = src[k];
+    }
+  }
+}
+
+inline unsigned arith_grid(long long items) {
+  long long blocks = (items + 255) / 256;
+  if (blocks > kMaxGrid) blocks = kMaxGrid;
+  if (blocks < 1) blocks = 1;
+  return (unsigned)blocks;
+}
+
+template <typename T, typename Op>
+void launch_arith_reduce_t(const void* own, const void* staged,
+                           int64_t stride_elems, int nranks, int me,
+                           void* out, int64_t n, hipStream_t stream) {
+  const long long esize = (long long)sizeof(typename T::S);
+  const long long stride_b = (long long)stride_elems * esize;
+  auto al16 = [](const void* p) {
+    return reinterpret_cast<uintptr_t>(p) % 16 == 0;
+  };
+  const bool vec = al16(own) && al16(out) && al16(staged) && stride_b % 16 == 0;
+  if (vec) {
+    const long long nvec = n / T::E;
+    const long long items = nvec + (n % T::E ? 1 : 0);
+    hipLaunchKernelGGL((arith_reduce_kernel<T, Op>), dim3(arith_grid(items)),
+                       dim3(256), 0, stream, static_cast<const char*>(own),
+                       static_cast<const char*>(staged), stride_b, nranks, me,
+                       static_cast<char*>(out), nvec, (long long)n);
+  } else {
+    hipLaunchKernelGGL((arith_reduce_kernel_scalar<T, Op>),
+                       dim3(arith_grid(n)), dim3(256), 0, stream,
+                       static_cast<const char*>(own),
+                       static_cast<const char*>(staged), stride_b, nranks, me,
+                       static_cast<char*>(out), (long long)n);
+  }
+}
+
+} // namespace
+
+void launch_arith_copy(const void* src, void* dst, int64_t nbytes,
+                       hipStream_t stream) {
+  if (nbytes <= 0) return;
+  if (reinterpret_cast<uintptr_t>(src) % 16 != 0 ||
+      reinterpret_cast<uintptr_t>(dst) % 16 != 0) {
+    // misaligned ends: the slab copy's phase-aligned head/body/tail
+    SlabDesc d;
+    d.src = src;
+    d.dst = dst;
+    d.before = 1;
+    d.count = 1;
+    d.after_b = nbytes;
+    d.src_pitch_b = nbytes;
+    d.dst_pitch_b = nbytes;
+    launch_slab_copy(&d, 1, stream);
+    return;
+  }
+  const long long nvec = nbytes / 16;
+  const long long items = nvec + (nbytes % 16 ? 1 : 0);
+  hipLaunchKernelGGL(arith_reduce_copy_kernel, dim3(arith_grid(items)),
+                     dim3(256), 0, stream, static_cast<const char*>(src),
+                     static_cast<char*>(dst), nvec, (long long)nbytes);
+}
+
+void launch_arith_reduce(const void* own, const void* staged,
+                         int64_t stride_elems, int nranks, int me, void* out,
+                         int64_t n_elems, int op, int dtype,
+                         hipStream_t stream) {
+  if (n_elems <= 0) return;
+  if (nranks == 1) {
+    launch_arith_copy(own, out, n_elems * (dtype == 0 ? 4 : 2), stream);
+    return;
+  }
+  auto dispatch = [&](auto opv) {
+    using Op = decltype(opv);
+    switch (dtype) {
+      case 0:
+        launch_arith_reduce_t<TF32, Op>(own, staged, stride_elems, nranks, me,
+                                        out, n_elems, stream);
+        break;
+      case 1:
+        launch_arith_reduce_t<TBF16, Op>(own, staged, stride_elems, nranks, me,
+                                         out, n_elems, stream);
+        break;
+      default:
+        launch_arith_reduce_t<TF16, Op>(own, staged, stride_elems, nranks, me,
+                                        out, n_elems, stream);
+        break;
     }
   };
   switch (op) {

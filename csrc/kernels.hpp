@@ -64,6 +64,25 @@ void launch_pairloc_reduce(const void* in, void* out, int64_t n_pairs,
 void launch_fp8_reduce(const void* in, void* out, int64_t n_elems,
                        int nranks, int op, bool e5m2, hipStream_t stream);
 
+// Arithmetic local reduction for bf16/fp16/fp32 that reads its sources where
+// they lie (the tail of native_allreduce): source r is `own` for r == me,
+// otherwise slot r (r < me) or r-1 (r > me) of `staged`, whose nranks-1
+// slots are stride_elems apart. Sources combine in rank order; 16-bit dtypes
+// accumulate in fp32 and round once (RNE); MIN/MAX follow fminf/fmaxf.
+// op: 0=sum 1=prod 2=min 3=max. dtype codes: 0=f32 1=bf16 2=f16.
+// nranks == 1 is launch_arith_copy of the own block (staged is not read).
+// Any n_elems and any alignment: 16-byte vectors when every pointer and the
+// slot stride allow it (tail elements by one extra work item), one element
+// per thread otherwise.
+void launch_arith_reduce(const void* own, const void* staged,
+                         int64_t stride_elems, int nranks, int me, void* out,
+                         int64_t n_elems, int op, int dtype,
+                         hipStream_t stream);
+// The nranks == 1 instance: raw bit copy of nbytes (no float conversion, so
+// it serves every dtype), one 16-byte nontemporal move per thread.
+void launch_arith_copy(const void* src, void* dst, int64_t nbytes,
+                       hipStream_t stream);
+
 // mxfp8 codec (csrc/mx8_kernels.hip): groups of 32 consecutive elements ->
 // 32 OCP e4m3fn payload bytes + one E8M0 scale byte (255 = non-finite
 // group). The rule is defined by the torch composite in csrc/ops.cpp; the

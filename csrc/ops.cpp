@@ -498,6 +498,169 @@ Tensor hierarchical_allreduce(Transport& tr, const Tensor& in, int64_t unit,
   return out;
 }
 
+bool arith_float_dtype(at::ScalarType t) {
+  return t == at::kFloat || t == at::kBFloat16 || t == at::kHalf;
+}
+
+int arith_dtype_code(at::ScalarType t) {
+  return t == at::kFloat ? 0 : (t == at::kBFloat16 ? 1 : 2);
+}
+
+int arith_op_code(int64_t op) {
+  return op == kSum ? 0 : (op == kProd ? 1 : (op == kMin ? 2 : 3));
+}
+
+// Torch-composite local reduce with the kernel's semantics (fp32
+// accumulation in rank order, one rounding): the CPU path of
+// native_allreduce. MIN/MAX inputs are NaN-free by contract — the kernel
+// follows fminf/fmaxf, at::minimum/maximum propagate NaN.
+Tensor arith_local_reduce(const std::vector<Tensor>& srcs, int kop,
+                          at::ScalarType out_dtype) {
+  auto acc = srcs[0].to(at::kFloat);
+  for (size_t r = 1; r < srcs.size(); ++r) {
+    auto v = srcs[r].to(at::kFloat);
+    if (kop == 0) acc = acc + v;
+    else if (kop == 1) acc = acc * v;
+    else if (kop == 2) acc = at::minimum(acc, v);
+    else acc = at::maximum(acc, v);
+  }
+  return acc.to(out_dtype);
+}
+
+// Two-shot allreduce on the framework's own reduce kernel: the same three
+// phases as hierarchical_allreduce (block exchange, local reduce of the
+// owned block, allgather), minus the work the result does not need:
+//   * the rank's own block is never copied into staging — staging holds
+//     P-1 slots, the grouped exchange carries no self pair, and the kernel
+//     reads the own block straight from the input;
+//   * at P == 1 there is no exchange, no staging and no allgather: the whole
+//     operation is one kernel launch, in -> out, on the caller's current
+//     stream (where every local reduce runs anyway), with no side-stream
+//     hop and no event pair because there is no wire phase. That launch is
+//     a typeless bit copy, so at P == 1 any dtype may come here.
+// Blocks are multiples of 16 bytes so every block start stays
+// vector-aligned; the last block takes the remainder.
+Tensor native_allreduce(Transport& tr, const Tensor& in, int64_t op) {
+  const int P = tr.size();
+  const int me = tr.rank();
+  const int64_t N = in.numel();
+  auto out = at::empty_like(in);
+  if (P == 1) {
+    if (in.is_cuda()) {
+      launch_arith_copy(in.data_ptr(), out.data_ptr(),
+                        N * (int64_t)in.element_size(),
+                        current_gpu_stream(in));
+    } else {
+      out.copy_(in);
+    }
+    return out;
+  }
+  TORCH_CHECK(arith_float_dtype(in.scalar_type()) && is_arith(op),
+              "native_allreduce reduces bf16/fp16/fp32 with sum/prod/min/max");
+  const int kop = arith_op_code(op);
+  const int64_t unit = 16 / (int64_t)in.element_size();
+  const int64_t nunits = N / unit;
+  std::vector<int64_t> counts(P);
+  for (int p = 0; p < P; ++p) {
+    counts[p] = (nunits / P + (p < nunits % P ? 1 : 0)) * unit;
+  }
+  counts[P - 1] += N - nunits * unit;
+  auto displs = prefix_displs(counts);
+  auto flat = in.view({-1});
+  auto out_flat = out.view({-1});
+  const int64_t mine = counts[me];
+  // slot stride rounded up to the vector so every slot starts aligned even
+  // when the owned block carries the remainder
+  const int64_t slot = (mine + unit - 1) / unit * unit;
+  // phase 1: my copy of block j goes to rank j (j != me); the P-1 peer
+  // copies of my block land in staging, rank order with me skipped
+  auto staging = at::empty({(int64_t)(P - 1) * slot}, in.options());
+  {
+    std::vector<Tensor> sends, recvs;
+    std::vector<int> speers, rpeers;
+    for (int p = 0; p < P; ++p) {
+      if (p == me) continue;
+      if (counts[p] > 0) {
+        sends.push_back(flat.narrow(0, displs[p], counts[p]));
+        speers.push_back(p);
+      }
+      if (mine > 0) {
+        recvs.push_back(
+            staging.narrow(0, (int64_t)(p - (p > me ? 1 : 0)) * slot, mine));
+        rpeers.push_back(p);
+      }
+    }
+    tr.exchange(sends, speers, recvs, rpeers);
+  }
+  // phase 2: reduce own block + P-1 staged copies into out's block
+  if (mine > 0) {
+    auto own = flat.narrow(0, displs[me], mine);
+    auto myblock = out_flat.narrow(0, displs[me], mine);
+    if (in.is_cuda()) {
+      launch_arith_reduce(own.data_ptr(), staging.data_ptr(), slot, P, me,
+                          myblock.data_ptr(), mine, kop,
+                          arith_dtype_code(in.scalar_type()),
+                          current_gpu_stream(in));
+    } else {
+      std::vector<Tensor> srcs;
+      for (int r = 0; r < P; ++r) {
+        srcs.push_back(r == me ? own
+                               : staging.narrow(
+                                     0, (int64_t)(r - (r > me ? 1 : 0)) * slot,
+                                     mine));
+      }
+      myblock.copy_(arith_local_reduce(srcs, kop, in.scalar_type()));
+    }
+  }
+  // phase 3: allgather the reduced blocks — one in-place RCCL allgather
+  // when the blocks are equal, grouped p2p otherwise and on gloo (whose
+  // allgather does not define input/output aliasing)
+  if (N % (unit * P) == 0 && tr.is_gpu()) {
+    auto myblock = out_flat.narrow(0, displs[me], mine);
+    tr.allgather_equal(myblock, out_flat);
+  } else {
+    std::vector<Tensor> s2, r2;
+    std::vector<int> sp, rp;
+    for (int p = 0; p < P; ++p) {
+      if (p == me) continue;
+      if (mine > 0) {
+        s2.push_back(out_flat.narrow(0, displs[me], mine));
+        sp.push_back(p);
+      }
+      if (counts[p] > 0) {
+        r2.push_back(out_flat.narrow(0, displs[p], counts[p]));
+        rp.push_back(p);
+      }
+    }
+    tr.exchange(s2, sp, r2, rp);
+  }
+  return out;
+}
+
+// Engine selection for the dtypes the transport's allreduce can carry
+// (Config::allreduce_engine, MPI4TORCH_AMD_ALLREDUCE).
+bool use_native_allreduce(const Transport& tr, at::ScalarType t, int64_t op) {
+  switch (config().allreduce_engine) {
+    case Config::kAllreduceRccl:
+      return false;
+    case Config::kAllreduceNative:
+      return arith_float_dtype(t) && is_arith(op);
+    default:
+      // a world of one only gets here under force_full_path on the GPU
+      return tr.size() == 1 && tr.is_gpu();
+  }
+}
+
+Tensor transport_or_native_allreduce(Transport& tr, const Tensor& in,
+                                     int64_t op) {
+  if (use_native_allreduce(tr, in.scalar_type(), op)) {
+    return native_allreduce(tr, in, op);
+  }
+  auto out = at::empty_like(in);
+  tr.allreduce(in, out, (RedOp)op);
+  return out;
+}
+
 int pairloc_dtype_code(at::ScalarType t) {
   switch (t) {
     case at::kFloat: return 0;
@@ -564,8 +727,10 @@ Tensor pairloc_lowered(Transport& tr, const Tensor& in, int64_t op) {
 Tensor allreduce_lowered(Transport& tr, const Tensor& in, int64_t op) {
   if (in.numel() == 0) return in.clone();
   if (tr.size() == 1) {
-    // force_full_path exercises the real machinery even alone: the native
-    // RCCL ring for arithmetic ops, the hierarchical exchange+kernel path
+    // force_full_path exercises the real machinery even alone:
+    // native_allreduce for arithmetic ops (one pass of the framework's own
+    // reduce kernel; MPI4TORCH_AMD_ALLREDUCE=rccl puts the degenerate
+    // ncclAllReduce back), the hierarchical exchange+kernel path
     // for bitwise/fp8/pairloc (P=1 self-exchange -> kernel -> in-place
     // allgather). Everything else short-circuits to a device clone.
     const bool fp8_in = in.scalar_type() == at::kFloat8_e4m3fn ||
@@ -584,8 +749,8 @@ Tensor allreduce_lowered(Transport& tr, const Tensor& in, int64_t op) {
     // land/lor/lxor lower to min/max/sum over 0/1 indicators; valid on any
     // dtype and on both transports (RCCL has no logical ops).
     auto ind = in.ne(0).to(at::kByte);
-    auto red = at::empty_like(ind);
-    tr.allreduce(ind, red, op == kLAnd ? kMin : (op == kLOr ? kMax : kSum));
+    auto red = transport_or_native_allreduce(
+        tr, ind, op == kLAnd ? kMin : (op == kLOr ? kMax : kSum));
     if (op == kLXor) red = red.bitwise_and_(1);
     return red.ne(0).to(in.scalar_type());
   }
@@ -622,9 +787,7 @@ Tensor allreduce_lowered(Transport& tr, const Tensor& in, int64_t op) {
   }
   TORCH_CHECK(is_arith(op));
   if (native_reduce_dtype(tr, in.scalar_type())) {
-    auto out = at::empty_like(in);
-    tr.allreduce(in, out, (RedOp)op);
-    return out;
+    return transport_or_native_allreduce(tr, in, op);
   }
   const bool fp8 = in.scalar_type() == at::kFloat8_e4m3fn ||
                    in.scalar_type() == at::kFloat8_e5m2;
@@ -656,9 +819,7 @@ Tensor allreduce_lowered(Transport& tr, const Tensor& in, int64_t op) {
         });
   }
   auto up = in.to(upcast_for_reduce(in.scalar_type()));
-  auto red = at::empty_like(up);
-  tr.allreduce(up, red, (RedOp)op);
-  return red.to(in.scalar_type());
+  return transport_or_native_allreduce(tr, up, op).to(in.scalar_type());
 }
 
 // ----------------------- mxfp8 compressed allreduce -----------------------
@@ -2396,6 +2557,29 @@ Tensor debug_fp8_reduce(const Tensor& stacked, int64_t op) {
   launch_fp8_reduce(in.data_ptr(), out.data_ptr(), out.numel(), (int)n,
                     (int)op, in.scalar_type() == at::kFloat8_e5m2,
                     current_gpu_stream(in));
+  return out;
+}
+
+// own: [n] (any element alignment, e.g. an offset view of a larger buffer);
+// staged: [nranks-1, n] with a contiguous last axis, row stride free.
+Tensor debug_arith_reduce(const Tensor& own, const Tensor& staged, int64_t me,
+                          int64_t op) {
+  TORCH_CHECK(own.is_cuda() && staged.is_cuda(),
+              "debug_arith_reduce is a GPU kernel test");
+  TORCH_CHECK(own.dim() == 1 && staged.dim() == 2 &&
+              staged.size(1) == own.size(0) &&
+              staged.scalar_type() == own.scalar_type() &&
+              own.stride(0) == 1 && (staged.size(1) <= 1 || staged.stride(1) == 1),
+              "debug_arith_reduce expects own [n] and staged [nranks-1, n]");
+  TORCH_CHECK(arith_float_dtype(own.scalar_type()) && is_arith(op));
+  const int64_t nranks = staged.size(0) + 1;
+  TORCH_CHECK(me >= 0 && me < nranks);
+  auto out = at::empty({own.size(0)}, own.options());
+  launch_arith_reduce(own.data_ptr(), staged.data_ptr(),
+                      nranks > 1 ? staged.stride(0) : 0, (int)nranks, (int)me,
+                      out.data_ptr(), own.size(0), arith_op_code(op),
+                      arith_dtype_code(own.scalar_type()),
+                      current_gpu_stream(own));
   return out;
 }
 

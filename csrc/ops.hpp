@@ -129,6 +129,10 @@ at::Tensor debug_pack_roundtrip(const at::Tensor& input, int64_t axis,
                                 std::vector<int64_t> counts);
 at::Tensor debug_bitwise_reduce(const at::Tensor& stacked, int64_t op);
 at::Tensor debug_fp8_reduce(const at::Tensor& stacked, int64_t op);
+// arith_reduce kernel: own [n] is source `me`, staged [nranks-1, n] holds
+// the other ranks in order; op is an MPI_* arithmetic constant.
+at::Tensor debug_arith_reduce(const at::Tensor& own, const at::Tensor& staged,
+                              int64_t me, int64_t op);
 // mxfp8 codec entry points: the torch composite for CPU tensors, the gfx950
 // kernels for GPU tensors (tests compare the two byte for byte).
 std::tuple<at::Tensor, at::Tensor> debug_mx8_quantize(const at::Tensor& x);

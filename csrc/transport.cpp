@@ -40,6 +40,14 @@ static void config_from_env(Config& c) {
   }
   const char* fh = std::getenv("MPI4TORCH_AMD_FORCE_HIERARCHICAL");
   c.force_hierarchical = fh && fh[0] == '1';
+  const char* ar = std::getenv("MPI4TORCH_AMD_ALLREDUCE");
+  const std::string arv = ar ? ar : "auto";
+  TORCH_CHECK(arv == "auto" || arv == "native" || arv == "rccl" || arv.empty(),
+              "MPI4TORCH_AMD_ALLREDUCE must be auto, native or rccl, got '",
+              arv, "'");
+  c.allreduce_engine = arv == "native" ? Config::kAllreduceNative
+                       : arv == "rccl" ? Config::kAllreduceRccl
+                                       : Config::kAllreduceAuto;
 }
 
 Config& config() {

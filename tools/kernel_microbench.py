@@ -119,7 +119,7 @@ def mx8_section(repeats=5):
     finally:
         C.force_full_path(False)
     line("w1 full-path AllreduceCompressed", tc, t.numel() * 2)
-    line("w1 full-path Allreduce (RCCL)", ta, t.numel() * 2)
+    line("w1 full-path Allreduce", ta, t.numel() * 2)
 
 
 if "--mx8" in sys.argv:
@@ -159,6 +159,30 @@ comm = m.COMM_WORLD
 ms = timeit(lambda: comm.Allreduce(t, m.MPI_SUM))
 report("w1 fast-path clone 64Mi fp32", ms, 2 * N * 4)
 del stk8, stki, stkp, x, t
+
+# arith_reduce, the local tail of native_allreduce. nranks=1 is the bit copy
+# the N=1 flagship times (1 GiB bf16), alternated with the slab copy
+# (fast_clone) at the same size; 8 x 128 MiB bf16 is the P=8 reduce.
+g1 = torch.randn(512 << 20, device="cuda", dtype=torch.bfloat16)  # 1 GiB
+none = g1.new_empty((0, g1.numel()))
+t_red, t_slab = [], []
+for _ in range(5):
+    t_red.append(timeit(lambda: m._C._arith_reduce(g1, none, 0, m.MPI_SUM)))
+    t_slab.append(timeit(lambda: comm.Allreduce(g1, m.MPI_SUM)))
+med = lambda v: sorted(v)[len(v) // 2]
+for name, ts in (("arith_reduce bf16 nranks=1 1GiB", t_red),
+                 ("slab copy (fast_clone) bf16 1GiB", t_slab)):
+    print(f"{name:34s} {med(ts)*1e3:9.1f} us  "
+          f"{2 * g1.numel() * 2 / med(ts) / 1e6:8.1f} GB/s  "
+          f"(min {min(ts)*1e3:.1f} max {max(ts)*1e3:.1f} us, 5 repeats)",
+          flush=True)
+del g1, none
+nb = 64 << 20  # 128 MiB of bf16 per rank
+own = torch.randn(nb, device="cuda", dtype=torch.bfloat16)
+stg = torch.randn(P - 1, nb, device="cuda", dtype=torch.bfloat16)
+ms = timeit(lambda: m._C._arith_reduce(own, stg, 0, m.MPI_SUM))
+report(f"arith_reduce bf16 P={P} 128MiB", ms, (P + 1) * nb * 2)
+del own, stg
 
 mx8_section()
 
