@@ -102,6 +102,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         [](bool enabled) { m4a::config().force_full_path = enabled; });
 
   m.def("_pack_roundtrip", &m4a::debug_pack_roundtrip);
+  m.def("_slab_copy", &m4a::debug_slab_copy);
   m.def("_bitwise_reduce", &m4a::debug_bitwise_reduce);
   m.def("_fp8_reduce", &m4a::debug_fp8_reduce);
   m.def("_arith_reduce", &m4a::debug_arith_reduce);

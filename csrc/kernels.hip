@@ -22,9 +22,10 @@
 // sides advance by after_b per axis element, so consecutive axis elements
 // are contiguous on BOTH sides). Rows are vectorized at the widest granule
 // whose alignment PHASE matches between src and dst ((src - dst) % G == 0):
-// each row gets a bytewise head up to dst 16/4/2-alignment, a granule body,
-// and a bytewise tail, so odd element counts and odd displacements still
-// stream at near-HBM rate instead of falling to a byte loop.
+// each row gets a bytewise head up to dst 16/8/4-alignment, a granule body,
+// and a bytewise tail; a sub-dword phase difference goes to the byte-window
+// kernel below. So odd element counts and odd displacements still stream at
+// near-HBM rate instead of falling to a byte loop.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp8.h>
@@ -395,14 +396,13 @@ __device__ inline float fp8_to_f32(unsigned char b) {
   return float(v);
 }
 
+// Unsaturated (the class constructors clamp to +-max first): a finite value
+// that rounds (RNE) past the largest finite fp8 comes out as NaN (e4m3fn:
+// |f| > 464) or +-inf (e5m2: |f| >= 61440), exactly as the torch cast the
+// CPU transport uses — an overflowed sum stays visible to a loss scaler.
 template <bool E5M2>
 __device__ inline unsigned char f32_to_fp8(float f) {
-  if (E5M2) {
-    __hip_fp8_e5m2 v(f);
-    return v.__x;
-  }
-  __hip_fp8_e4m3 v(f);
-  return v.__x;
+  return __hip_cvt_float_to_fp8(f, __HIP_NOSAT, E5M2 ? __HIP_E5M2 : __HIP_E4M3);
 }
 
 struct FAdd {
@@ -416,6 +416,18 @@ struct FMin {
 };
 struct FMax {
   __device__ static float apply(float a, float b) { return fmaxf(a, b); }
+};
+// fp8 reduce MIN/MAX: a NaN in any source makes the result NaN
+// (at::minimum/at::maximum on the CPU transport); fminf/fmaxf would drop it.
+struct FMinNan {
+  __device__ static float apply(float a, float b) {
+    return (a != a || b != b) ? __builtin_nanf("") : fminf(a, b);
+  }
+};
+struct FMaxNan {
+  __device__ static float apply(float a, float b) {
+    return (a != a || b != b) ? __builtin_nanf("") : fmaxf(a, b);
+  }
 };
 
 // 16 elements per thread via 16-byte (dwordx4) loads; fp32 accumulators.
@@ -460,7 +472,7 @@ __global__ __launch_bounds__(256) void fp8_reduce_kernel(
   }
 }
 
-// scalar tail/general path (n not divisible by 8, or unaligned)
+// general path (n not divisible by 16, or unaligned)
 template <typename Op, bool E5M2>
 __global__ __launch_bounds__(256) void fp8_reduce_kernel_scalar(
     const unsigned char* __restrict__ in, unsigned char* __restrict__ out,
@@ -516,8 +528,8 @@ void launch_fp8_reduce(const void* in, void* out, int64_t n_elems, int nranks,
   switch (op) {
     case 0: dispatch(FAdd{}); break;
     case 1: dispatch(FMul{}); break;
-    case 2: dispatch(FMin{}); break;
-    default: dispatch(FMax{}); break;
+    case 2: dispatch(FMinNan{}); break;
+    default: dispatch(FMaxNan{}); break;
   }
 }
 
@@ -800,7 +812,8 @@ void launch_arith_reduce(const void* own, const void* staged,
 // the op layer allgathers the (value, location) pairs and this kernel does
 // the arg-reduce locally — completing the reference's 12-op table
 // (reference csrc/extension.cpp:204-252). Tie-break: smallest location
-// (MPI-defined).
+// (MPI-defined). A NaN value wins for both ops (as torch.min/torch.max
+// propagate it), with the smallest location among the NaN entries.
 // ---------------------------------------------------------------------------
 
 #include <hip/hip_fp16.h>
@@ -819,7 +832,27 @@ __device__ inline bool pl_lt<hip_bfloat16>(hip_bfloat16 a, hip_bfloat16 b) {
   return (float)a < (float)b;
 }
 template <typename T>
-__device__ inline bool pl_eq(T a, T b) { return !pl_lt(a, b) && !pl_lt(b, a); }
+__device__ inline bool pl_eq(T a, T b) { return a == b; }
+template <>
+__device__ inline bool pl_eq<__half>(__half a, __half b) {
+  return (float)a == (float)b;
+}
+template <>
+__device__ inline bool pl_eq<hip_bfloat16>(hip_bfloat16 a, hip_bfloat16 b) {
+  return (float)a == (float)b;
+}
+template <typename T>
+__device__ inline bool pl_nan(T) { return false; }  // integral dtypes
+template <>
+__device__ inline bool pl_nan<float>(float a) { return a != a; }
+template <>
+__device__ inline bool pl_nan<double>(double a) { return a != a; }
+template <>
+__device__ inline bool pl_nan<__half>(__half a) { return (float)a != (float)a; }
+template <>
+__device__ inline bool pl_nan<hip_bfloat16>(hip_bfloat16 a) {
+  return (float)a != (float)a;
+}
 
 template <typename T, bool MAXLOC>
 __global__ __launch_bounds__(256) void pairloc_reduce_kernel(
@@ -833,11 +866,16 @@ __global__ __launch_bounds__(256) void pairloc_reduce_kernel(
     for (long long r = 1; r < nranks; ++r) {
       const T v = in[r * 2 * n + 2 * i];
       const T l = in[r * 2 * n + 2 * i + 1];
-      const bool better = MAXLOC ? pl_lt(bv, v) : pl_lt(v, bv);
-      if (better || (pl_eq(v, bv) && pl_lt(l, bl))) {
-        bv = v;
-        bl = l;
-      }
+      // a NaN value beats every number and ties only with another NaN
+      // (pl_lt and pl_eq are false whenever a NaN is involved). Bitwise
+      // operators and selects keep the loop body free of branches.
+      const bool vn = pl_nan(v), bn = pl_nan(bv);
+      const bool better =
+          (vn & !bn) | (MAXLOC ? pl_lt(bv, v) : pl_lt(v, bv));
+      const bool tie = pl_eq(v, bv) | (vn & bn);
+      const bool take = better | (tie & pl_lt(l, bl));
+      bv = take ? v : bv;
+      bl = take ? l : bl;
     }
     out[2 * i] = bv;
     out[2 * i + 1] = bl;

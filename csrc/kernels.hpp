@@ -18,7 +18,7 @@ namespace m4a {
 // All quantities in BYTES except `before`/`count` (row counts). Note the
 // c-stride is after_b on BOTH sides by definition, so (count, after)
 // collapse into one contiguous row of count*after_b bytes per b — the
-// kernel exploits this and vectorizes rows with phase-aligned 16/8/4/2-byte
+// kernel exploits this and vectorizes rows with phase-aligned 16/8/4-byte
 // granules plus bytewise head/tail.
 struct SlabDesc {
   const void* src;
@@ -34,8 +34,9 @@ struct SlabDesc {
 // by value in kernel args). Larger batches loop over launches.
 constexpr int kMaxSlabsPerLaunch = 8;
 
-// Batched strided copy of `n` slabs on `stream`. Picks the widest access
-// (16B/4B/1B) every slab admits; one launch per <=8 slabs.
+// Batched strided copy of `n` slabs on `stream`. Consecutive slabs that admit
+// the same granule (16, 8 or 4 bytes by the src/dst phase and pitch
+// difference, else the 16-byte byte-window kernel) share launches of <=8.
 void launch_slab_copy(const SlabDesc* descs, int n, hipStream_t stream);
 
 // Elementwise bitwise reduction across `nranks` contiguous chunks:
@@ -52,6 +53,9 @@ void launch_bitwise_reduce(const void* in, void* out, int64_t chunk_bytes,
 // value, location in the same dtype), out is [n_pairs][2].
 //   op 0 = MINLOC: smallest value, ties -> smallest location
 //   op 1 = MAXLOC: largest value, ties -> smallest location
+// A NaN value wins for both ops (torch.min/torch.max propagate it); its
+// location is the smallest among the NaN entries. -0.0 and +0.0 tie.
+// Locations compare exactly in their own dtype and must not be NaN.
 // dtype codes: 0=f32 1=f64 2=f16 3=bf16 4=i8 5=u8 6=i16 7=i32 8=i64
 void launch_pairloc_reduce(const void* in, void* out, int64_t n_pairs,
                            int nranks, int op, int dtype, hipStream_t stream);
@@ -60,6 +64,10 @@ void launch_pairloc_reduce(const void* in, void* out, int64_t n_pairs,
 //   out[i] = op_{r<nranks} fp32(in[r*n + i])  quantized to fp8 ONCE.
 // This is the MI355X fp8 allreduce tail (allgather + this kernel): one
 // quantization instead of one per ring hop, fp32 accumulation throughout.
+// The result is the torch cast of the fp32 rank-order accumulation: round to
+// nearest even WITHOUT saturation, so a finite overflow gives NaN (e4m3fn,
+// |acc| > 464) or +-inf (e5m2, |acc| >= 61440) and a loss scaler still sees
+// it. MIN/MAX propagate NaN (at::minimum/at::maximum, unlike arith_reduce).
 // op: 0=sum 1=prod 2=min 3=max; e5m2 selects the encoding.
 void launch_fp8_reduce(const void* in, void* out, int64_t n_elems,
                        int nranks, int op, bool e5m2, hipStream_t stream);

@@ -679,16 +679,26 @@ int pairloc_dtype_code(at::ScalarType t) {
 }
 
 // Torch-composite pair arg-reduce over stk [n_chunks, n_pairs, 2]: the CPU
-// path and the reference semantics the CDNA4 kernel is tested against.
+// path, same rule as the CDNA4 kernel (csrc/kernels.hpp). min/max propagate
+// NaN, so a NaN value wins and the NaN entries are the ones whose locations
+// compete. Integral locations stay int64: a double cannot tell neighbours
+// above 2^53 apart.
 Tensor pairloc_local_reduce(const Tensor& stk, int64_t kop,
                             at::ScalarType out_dtype) {
   auto vals = stk.select(2, 0);
-  auto locs = stk.select(2, 1).to(at::kDouble);
+  const bool fl = at::isFloatingType(vals.scalar_type());
+  auto locs = stk.select(2, 1).to(fl ? at::kDouble : at::kLong);
   Tensor bestv =
       kop == 0 ? std::get<0>(vals.min(0)) : std::get<0>(vals.max(0));
   auto mask = vals.eq(bestv.unsqueeze(0));
-  auto masked = locs.masked_fill(mask.logical_not(),
-                                 std::numeric_limits<double>::infinity());
+  if (fl) {
+    mask = mask.logical_or(
+        vals.isnan().logical_and(bestv.isnan().unsqueeze(0)));
+  }
+  const at::Scalar never =
+      fl ? at::Scalar(std::numeric_limits<double>::infinity())
+         : at::Scalar(std::numeric_limits<int64_t>::max());
+  auto masked = locs.masked_fill(mask.logical_not(), never);
   auto bestl = std::get<0>(masked.min(0)).to(out_dtype);
   return at::stack({bestv, bestl}, -1);
 }
@@ -2546,6 +2556,76 @@ Tensor debug_pack_roundtrip(const Tensor& input, int64_t axis,
   return out;
 }
 
+// One launch_slab_copy call over caller-chosen descriptors (byte offsets
+// into two flat uint8 tensors). Every descriptor is bounds-checked on the
+// host before anything is launched, so a wrong test raises instead of
+// touching memory outside the tensors.
+void debug_slab_copy(const Tensor& src, const Tensor& dst,
+                     const std::vector<std::vector<int64_t>>& descs) {
+  TORCH_CHECK(src.is_cuda() && dst.is_cuda() && src.device() == dst.device(),
+              "debug_slab_copy is a GPU kernel test");
+  TORCH_CHECK(src.scalar_type() == at::kByte && dst.scalar_type() == at::kByte &&
+                  src.dim() == 1 && dst.dim() == 1 && src.is_contiguous() &&
+                  dst.is_contiguous(),
+              "debug_slab_copy expects flat contiguous uint8 tensors");
+  constexpr int64_t kMaxBytes = int64_t(1) << 31;  // keeps the products exact
+  TORCH_CHECK(src.numel() < kMaxBytes && dst.numel() < kMaxBytes);
+  const char* sbase = static_cast<const char*>(src.data_ptr());
+  char* dbase = static_cast<char*>(dst.data_ptr());
+  TORCH_CHECK(sbase + src.numel() <= dbase || dbase + dst.numel() <= sbase,
+              "debug_slab_copy: src and dst overlap");
+  // [begin, end) of the bytes a slab spans on one side; empty slabs span
+  // nothing but must still start inside the tensor
+  auto span = [](int64_t off, int64_t before, int64_t row_b, int64_t pitch,
+                 int64_t numel, size_t i, const char* side) {
+    TORCH_CHECK(off >= 0 && off <= numel && before >= 0 && before <= numel &&
+                    row_b >= 0 && row_b <= numel && pitch >= 0 &&
+                    pitch <= numel,
+                "debug_slab_copy: descriptor ", i, " out of range on ", side);
+    if (before == 0 || row_b == 0) return std::make_pair(off, off);
+    const int64_t end = off + (before - 1) * pitch + row_b;
+    TORCH_CHECK(end <= numel, "debug_slab_copy: descriptor ", i,
+                " runs past the end of ", side);
+    return std::make_pair(off, end);
+  };
+  std::vector<SlabDesc> slabs;
+  std::vector<std::pair<int64_t, int64_t>> dspans;
+  slabs.reserve(descs.size());
+  for (size_t i = 0; i < descs.size(); ++i) {
+    const auto& t = descs[i];
+    TORCH_CHECK(t.size() == 7,
+                "debug_slab_copy: descriptor is (src_off, dst_off, before, "
+                "count, after_b, src_pitch_b, dst_pitch_b)");
+    const int64_t before = t[2], count = t[3], after_b = t[4];
+    TORCH_CHECK(count >= 0 && after_b >= 0 &&
+                    (count == 0 || after_b <= kMaxBytes / count),
+                "debug_slab_copy: descriptor ", i, " row size out of range");
+    const int64_t row_b = count * after_b;
+    span(t[0], before, row_b, t[5], src.numel(), i, "src");
+    const auto d = span(t[1], before, row_b, t[6], dst.numel(), i, "dst");
+    TORCH_CHECK(before <= 1 || row_b == 0 || t[6] >= row_b,
+                "debug_slab_copy: descriptor ", i, " dst rows overlap");
+    if (d.second > d.first) dspans.push_back(d);
+    SlabDesc s;
+    s.src = sbase + t[0];
+    s.dst = dbase + t[1];
+    s.before = before;
+    s.count = count;
+    s.after_b = after_b;
+    s.src_pitch_b = t[5];
+    s.dst_pitch_b = t[6];
+    slabs.push_back(s);
+  }
+  std::sort(dspans.begin(), dspans.end());
+  for (size_t i = 1; i < dspans.size(); ++i) {
+    TORCH_CHECK(dspans[i - 1].second <= dspans[i].first,
+                "debug_slab_copy: destination ranges overlap");
+  }
+  TORCH_CHECK(slabs.size() < (size_t)std::numeric_limits<int>::max());
+  if (slabs.empty()) return;
+  launch_slab_copy(slabs.data(), (int)slabs.size(), current_gpu_stream(src));
+}
+
 Tensor debug_fp8_reduce(const Tensor& stacked, int64_t op) {
   TORCH_CHECK(stacked.is_cuda(), "debug_fp8_reduce is a GPU kernel test");
   TORCH_CHECK(stacked.dim() >= 2);
@@ -2651,7 +2731,7 @@ Tensor debug_pairloc_reduce(const Tensor& stacked, int64_t op) {
                           current_gpu_stream(in));
     return out;
   }
-  // CPU reference composite — what the CDNA4 kernel is compared against
+  // CPU composite (the gloo transport's path)
   return pairloc_local_reduce(in.view({n, -1, 2}), op, in.scalar_type())
       .view(out_sizes)
       .contiguous();

@@ -127,6 +127,12 @@ at::Tensor join_dummies(const at::Tensor& loopthrough,
 // bitwise-reduce kernels directly, without a multi-rank world.
 at::Tensor debug_pack_roundtrip(const at::Tensor& input, int64_t axis,
                                 std::vector<int64_t> counts);
+// launch_slab_copy once over descs, each (src_off, dst_off, before, count,
+// after_b, src_pitch_b, dst_pitch_b) in bytes into the flat uint8 tensors
+// src and dst. Raises before launching if a descriptor leaves either tensor
+// or two destination ranges overlap.
+void debug_slab_copy(const at::Tensor& src, const at::Tensor& dst,
+                     const std::vector<std::vector<int64_t>>& descs);
 at::Tensor debug_bitwise_reduce(const at::Tensor& stacked, int64_t op);
 at::Tensor debug_fp8_reduce(const at::Tensor& stacked, int64_t op);
 // arith_reduce kernel: own [n] is source `me`, staged [nranks-1, n] holds

@@ -2,9 +2,8 @@
 
 Kernel numerics are checked bit for bit against a torch reference with the
 kernel's contract: sources combined in rank order, fp32 accumulation, one
-round-to-nearest-even cast. MIN/MAX follow fminf/fmaxf (as the fp8 reduce
-kernel does); they differ from torch.minimum/maximum only on NaN, so the
-arithmetic inputs are NaN-free. The P = 1 instance is a raw bit copy and is
+round-to-nearest-even cast. MIN/MAX follow fminf/fmaxf; inputs with NaN are
+in test_gpu_kernel_edges.py. The P = 1 instance is a raw bit copy and is
 fed arbitrary bit patterns (NaN payloads, infinities, -0.0, subnormals).
 """
 
