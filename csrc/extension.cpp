@@ -50,6 +50,8 @@ static auto communicator_class =
         .def("Gather", &Communicator::Gather)
         .def("Allgather", &Communicator::Allgather)
         .def("Reducescatter", &Communicator::Reducescatter)
+        .def("ReducescatterCompressed",
+             &Communicator::ReducescatterCompressed)
         .def("Scatter", &Communicator::Scatter)
         .def("Alltoall", &Communicator::Alltoall)
         .def("Alltoallv", &Communicator::Alltoallv)
@@ -110,6 +112,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("_mx8_quantize", &m4a::debug_mx8_quantize);
   m.def("_mx8_reduce", &m4a::debug_mx8_reduce);
   m.def("_mx8_dequantize", &m4a::debug_mx8_dequantize, py::arg("payload"),
+        py::arg("scales"), py::arg("numel"), py::arg("dtype"),
+        py::arg("out") = c10::optional<at::Tensor>());
+  m.def("_mx8_reduce_to", &m4a::debug_mx8_reduce_to, py::arg("payload"),
         py::arg("scales"), py::arg("numel"), py::arg("dtype"),
         py::arg("out") = c10::optional<at::Tensor>());
   m.def("reload_config", &m4a::reload_config_from_env);

@@ -109,5 +109,13 @@ void launch_mx8_reduce(const void* payload_in, const void* scales_in,
 // Dequantize into exactly n_elems elements of the given dtype (RNE).
 void launch_mx8_dequantize(const void* payload, const void* scales, void* out,
                            int64_t n_elems, int dtype, hipStream_t stream);
+// Reduce nranks mxfp8 copies of ceil(n_elems/32) groups straight into
+// n_elems elements of `dtype` (0=f32 1=bf16 2=f16): fp32 rank-order sum of
+// dequantized values, one RNE cast, no requantization. Writes exactly
+// n_elems elements. Input layout as launch_mx8_reduce with
+// n_groups = ceil(n_elems/32). nranks == 1 is launch_mx8_dequantize.
+void launch_mx8_reduce_to(const void* payload_in, const void* scales_in,
+                          void* out, int64_t n_elems, int nranks, int dtype,
+                          hipStream_t stream);
 
 } // namespace m4a

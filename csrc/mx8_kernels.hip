@@ -14,7 +14,7 @@
 //     hardware RNE f32->e4m3 of hip_fp8.h, which cannot saturate because
 //     amax*2^-E <= 448 by construction.
 //
-// Three streaming kernels, all 256-thread workgroups, grid-stride, 16-byte
+// Four streaming kernels, all 256-thread workgroups, grid-stride, 16-byte
 // accesses on the wide side, nontemporal (every byte is touched once):
 //   quantize   : 8 lanes x 16 B per fp32 group, 4 lanes x 16 B per 16-bit
 //                group; amax crosses the lanes with 3 / 2 xor-shuffles;
@@ -25,6 +25,10 @@
 //                accumulators, P copies summed in rank order on dequantized
 //                values, requantization fused (amax crosses the lane pair).
 //   dequantize : mirror of quantize; writes exactly N elements.
+//   reduce_to  : the reduce-scatter tail — the reduce kernel without its
+//                requantization: P copies summed in rank order straight
+//                into N elements of the output dtype, 32 output bytes per
+//                lane (two 16-byte stores).
 // Each has a one-thread-per-group scalar twin for base pointers that miss
 // the vector alignment (e.g. a contiguous x[1:] view); the partial last
 // group of the vector kernels goes through the same scalar group routine.
@@ -442,6 +446,128 @@ __global__ __launch_bounds__(256) void mx8_dequantize_kernel_scalar(
   }
 }
 
+// ---- reduce_to (the reduce-scatter tail) ---------------------------------
+//
+// P copies of G = ceil(N/32) groups -> N elements of the output dtype: fp32
+// rank-order sum of dequantized values, one RNE cast, no requantization.
+// Input layout as mx8_reduce_kernel: pin [nranks][G*32], sin [nranks][G].
+
+// One group, any alignment, cnt <= 32 elements written.
+template <int K>
+__device__ inline void reduce_to_group_scalar(
+    const u8* __restrict__ pin, const u8* __restrict__ sin, long long G,
+    long long g, long long nranks, int cnt,
+    typename Elem<K>::type* __restrict__ out) {
+  bool bad = false;
+  for (long long r = 0; r < nranks; ++r) bad = bad || sin[r * G + g] == 255;
+  for (int k = 0; k < cnt; ++k) {
+    float a = ldexpf(e4m3_to_f32(pin[g * 32 + k]), (int)sin[g] - 127);
+    for (long long r = 1; r < nranks; ++r) {
+      a += ldexpf(e4m3_to_f32(pin[(r * G + g) * 32 + k]),
+                  (int)sin[r * G + g] - 127);
+    }
+    out[k] = f32_to_elem<K>(bad ? __uint_as_float(kQNaNBits) : a);
+  }
+}
+
+// Vector body: every lane produces 32 output bytes, two consecutive 16-byte
+// stores, so BPL payload bytes (= elements) per lane per copy are 8 for
+// fp32 (dwordx2 loads, 4 lanes per group) and 16 for the 16-bit dtypes (the
+// reduce kernel's dwordx4 loads, 2 lanes per group). Measured against the
+// other widths in doc/kernels.md section 5: four stores per lane (fp32 at
+// the reduce kernel's width) leave each 128-byte line to four store
+// instructions and run at half the rate; one store per lane (the
+// dequantize kernel's width) keeps too few load bytes in flight.
+template <int BPL>
+__device__ inline void load_payload(const u8* __restrict__ pin, long long j,
+                                    unsigned (&w)[BPL / 4]) {
+  if constexpr (BPL == 8) {
+    const v2u t =
+        __builtin_nontemporal_load(reinterpret_cast<const v2u*>(pin) + j);
+    w[0] = t[0];
+    w[1] = t[1];
+  } else {
+    const v4u t =
+        __builtin_nontemporal_load(reinterpret_cast<const v4u*>(pin) + j);
+    for (int d = 0; d < 4; ++d) w[d] = t[d];
+  }
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void mx8_reduce_to_kernel(
+    const u8* __restrict__ pin, const u8* __restrict__ sin,
+    void* __restrict__ out, long long nfull, long long G, long long N,
+    long long nranks) {
+  using T = typename Elem<K>::type;
+  constexpr int EPS = K == kF32 ? 4 : 8;          // elements per 16-B store
+  constexpr int NS = 2;                           // 16-byte stores per lane
+  constexpr int BPL = NS * EPS;                   // payload bytes per lane
+  constexpr int LPG = 32 / BPL;                   // lanes per group
+  constexpr int DW = BPL / 4;                     // payload dwords per lane
+  const long long total = nfull * LPG;            // lane slots in the body
+  const long long cstride = G * LPG;              // lane slots per copy
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+       i < total; i += stride) {
+    const long long g = i / LPG;
+    float acc[BPL];
+    bool bad;
+    {
+      unsigned w[DW];
+      load_payload<BPL>(pin, i, w);
+      const int sb = sin[g];
+      bad = sb == 255;
+      for (int d = 0; d < DW; ++d) {
+        for (int k = 0; k < 4; ++k) {
+          acc[4 * d + k] =
+              ldexpf(e4m3_to_f32((u8)(w[d] >> (8 * k))), sb - 127);
+        }
+      }
+    }
+    for (long long r = 1; r < nranks; ++r) {
+      unsigned w[DW];
+      load_payload<BPL>(pin, r * cstride + i, w);
+      const int sb = sin[r * G + g];
+      bad = bad || sb == 255;
+      for (int d = 0; d < DW; ++d) {
+        for (int k = 0; k < 4; ++k) {
+          acc[4 * d + k] +=
+              ldexpf(e4m3_to_f32((u8)(w[d] >> (8 * k))), sb - 127);
+        }
+      }
+    }
+    v4u* o = reinterpret_cast<v4u*>(out) + i * NS;
+    for (int s = 0; s < NS; ++s) {
+      float x[EPS];
+      for (int k = 0; k < EPS; ++k) {
+        x[k] = bad ? __uint_as_float(kQNaNBits) : acc[s * EPS + k];
+      }
+      __builtin_nontemporal_store(pack16<K, EPS>(x), o + s);
+    }
+  }
+  // partial last group: exactly N - 32*nfull elements, nothing past N
+  const int tail = (int)(N - nfull * 32);
+  if (tail > 0 && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+    reduce_to_group_scalar<K>(pin, sin, G, nfull, nranks, tail,
+                              reinterpret_cast<T*>(out) + nfull * 32);
+  }
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void mx8_reduce_to_kernel_scalar(
+    const u8* __restrict__ pin, const u8* __restrict__ sin,
+    void* __restrict__ out, long long G, long long N, long long nranks) {
+  using T = typename Elem<K>::type;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < G;
+       g += stride) {
+    const long long left = N - g * 32;
+    reduce_to_group_scalar<K>(pin, sin, G, g, nranks,
+                              left < 32 ? (int)left : 32,
+                              reinterpret_cast<T*>(out) + g * 32);
+  }
+}
+
 inline unsigned grid_for(long long work) {
   long long blocks = (work + 255) / 256;
   if (blocks > 4096) blocks = 4096;
@@ -488,7 +614,39 @@ void launch_dequantize_t(const void* pay, const void* sc, void* out, int64_t N,
   }
 }
 
+template <int K>
+void launch_reduce_to_t(const u8* pin, const u8* sin, void* out, int64_t N,
+                        int nranks, hipStream_t stream) {
+  const long long G = (N + 31) / 32;
+  const long long nfull = N / 32;
+  // The vector body indexes every copy from pin with stride G*32, a multiple
+  // of 16, so an aligned base keeps every copy aligned.
+  if (aligned(pin, 16) && aligned(out, 16)) {
+    hipLaunchKernelGGL((mx8_reduce_to_kernel<K>),
+                       dim3(grid_for(nfull * (K == kF32 ? 4 : 2))), dim3(256),
+                       0, stream, pin, sin, out, nfull, G, (long long)N,
+                       (long long)nranks);
+  } else {
+    hipLaunchKernelGGL((mx8_reduce_to_kernel_scalar<K>), dim3(grid_for(G)),
+                       dim3(256), 0, stream, pin, sin, out, G, (long long)N,
+                       (long long)nranks);
+  }
+}
+
 } // namespace
+
+void launch_mx8_reduce_to(const void* payload_in, const void* scales_in,
+                          void* out, int64_t n_elems, int nranks, int dtype,
+                          hipStream_t stream) {
+  if (n_elems <= 0) return;
+  const u8* pin = static_cast<const u8*>(payload_in);
+  const u8* sin = static_cast<const u8*>(scales_in);
+  switch (dtype) {
+    case 0: launch_reduce_to_t<kF32>(pin, sin, out, n_elems, nranks, stream); break;
+    case 1: launch_reduce_to_t<kBF16>(pin, sin, out, n_elems, nranks, stream); break;
+    default: launch_reduce_to_t<kF16>(pin, sin, out, n_elems, nranks, stream); break;
+  }
+}
 
 void launch_mx8_quantize(const void* in, void* payload, void* scales,
                          int64_t n_elems, int dtype, hipStream_t stream) {

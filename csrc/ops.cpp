@@ -947,6 +947,83 @@ Tensor mx8_dequantize(const Tensor& pay, const Tensor& sc, int64_t numel,
   return d.narrow(0, 0, numel).to(dtype);
 }
 
+// P copies: pin [P * G*32], sin [P * G], G = ceil(numel/32) -> flat [numel]
+// of `dtype` (views ok). The reduce-scatter tail, normative here: fp32
+// rank-order sum of the dequantized copies, then .to(dtype) — no
+// requantization. A 255 scale in any copy makes that group NaN.
+Tensor mx8_reduce_to(const Tensor& pin, const Tensor& sin, int64_t numel,
+                     int P, at::ScalarType dtype) {
+  const int dt = mx8_dtype_code(dtype);
+  if (pin.is_cuda()) {
+    auto out = at::empty({numel}, pin.options().dtype(dtype));
+    launch_mx8_reduce_to(pin.data_ptr(), sin.data_ptr(), out.data_ptr(),
+                         numel, P, dt, current_gpu_stream(pin));
+    return out;
+  }
+  const int64_t G = (numel + 31) / 32;
+  auto pv = pin.view({P, G, 32});
+  auto sv = sin.view({P, G});
+  auto acc = mx8_dequantize_groups(pv[0], sv[0]);
+  for (int r = 1; r < P; ++r) {
+    acc = acc + mx8_dequantize_groups(pv[r], sv[r]);
+  }
+  return acc.view({-1}).narrow(0, 0, numel).to(dtype);
+}
+
+// The reduce-scatter sibling of mx8_allreduce, phases 1-2 only: `packed` is
+// the rank-major packed input, P blocks of L elements (block p is what rank
+// p keeps). Each block is quantized in groups of 32 that start at the
+// block's first element, block p travels to rank p (payload and scales as
+// two contiguous pieces per peer in ONE grouped call) and the P copies of
+// the owned block are summed straight into the input dtype. Every value is
+// quantized exactly once; nothing goes back on the wire. Staging is two
+// buffers of ~33/32 * P*L bytes; the wire carries (P-1)*33*ceil(L/32) bytes
+// per rank.
+Tensor mx8_reducescatter(Transport& tr, const Tensor& packed, int64_t L) {
+  const int P = tr.size();
+  const int64_t Gb = (L + 31) / 32;
+  auto bopts = packed.options().dtype(at::kByte);
+  Tensor pay, sc;
+  if (L % 32 == 0) {
+    // block-relative groups coincide with flat groups: one launch
+    auto q = mx8_quantize(packed);
+    pay = q.first;
+    sc = q.second;
+  } else {
+    // one launch per block; a block base off 16 bytes takes the scalar twin
+    pay = at::empty({(int64_t)P * Gb * 32}, bopts);
+    sc = at::empty({(int64_t)P * Gb}, bopts);
+    for (int p = 0; p < P; ++p) {
+      auto blk = packed.narrow(0, (int64_t)p * L, L);
+      if (packed.is_cuda()) {
+        launch_mx8_quantize(blk.data_ptr(),
+                            pay.narrow(0, (int64_t)p * Gb * 32, Gb * 32)
+                                .data_ptr(),
+                            sc.narrow(0, (int64_t)p * Gb, Gb).data_ptr(), L,
+                            mx8_dtype_code(packed.scalar_type()),
+                            current_gpu_stream(packed));
+      } else {
+        auto q = mx8_quantize(blk);
+        pay.narrow(0, (int64_t)p * Gb * 32, Gb * 32).copy_(q.first);
+        sc.narrow(0, (int64_t)p * Gb, Gb).copy_(q.second);
+      }
+    }
+  }
+  auto stg_pay = at::empty({(int64_t)P * Gb * 32}, bopts);
+  auto stg_sc = at::empty({(int64_t)P * Gb}, bopts);
+  std::vector<Tensor> sends(2 * P), recvs(2 * P);
+  std::vector<int> peers(2 * P);
+  for (int p = 0; p < P; ++p) {
+    sends[2 * p] = pay.narrow(0, (int64_t)p * Gb * 32, Gb * 32);
+    sends[2 * p + 1] = sc.narrow(0, (int64_t)p * Gb, Gb);
+    recvs[2 * p] = stg_pay.narrow(0, (int64_t)p * Gb * 32, Gb * 32);
+    recvs[2 * p + 1] = stg_sc.narrow(0, (int64_t)p * Gb, Gb);
+    peers[2 * p] = peers[2 * p + 1] = p;
+  }
+  tr.exchange(sends, peers, recvs, peers);
+  return mx8_reduce_to(stg_pay, stg_sc, L, P, packed.scalar_type());
+}
+
 // The mxfp8 sibling of hierarchical_allreduce: quantize once, exchange each
 // rank's copy of group-block j to rank j (payload and scales as two
 // contiguous pieces per peer in ONE grouped call), fused
@@ -1840,6 +1917,88 @@ Tensor Communicator::Reducescatter(const Tensor& input, int64_t axis,
 }
 
 // ---------------------------------------------------------------------------
+// ReducescatterCompressed (MI355X extension; not in the reference API)
+// ---------------------------------------------------------------------------
+
+namespace {
+struct ReducescatterCompressedBackward : public M4ANode {
+  explicit ReducescatterCompressedBackward(int64_t axis) : axis(axis) {}
+  std::string name() const override {
+    return "M4AReducescatterCompressedBackward";
+  }
+  variable_list apply(variable_list&& grads) override {
+    variable_list out(1);
+    if (should_compute_output(0)) {
+      // exact adjoint of the sum; quantization is straight-through and the
+      // gradient travels uncompressed
+      out[0] = comm->Allgather(grads[0], axis);
+    }
+    return out;
+  }
+  int64_t axis;
+};
+} // namespace
+
+Tensor Communicator::ReducescatterCompressed(const Tensor& input,
+                                             int64_t axis) {
+  TORCH_CHECK(input.scalar_type() == at::kFloat ||
+                  input.scalar_type() == at::kBFloat16 ||
+                  input.scalar_type() == at::kHalf,
+              "mpi4torch_amd: ReducescatterCompressed supports float32, "
+              "bfloat16 and float16 tensors, got ", input.scalar_type());
+  axis = at::maybe_wrap_dim(axis, input.dim());
+  std::shared_ptr<M4ANode> grad_fn;
+  if (torch::autograd::compute_requires_grad(input)) {
+    grad_fn = make_node<ReducescatterCompressedBackward>(
+        c10::intrusive_ptr<Communicator>::unsafe_reclaim_from_nonowning(this),
+        axis);
+    grad_fn->set_next_edges(torch::autograd::collect_next_edges(input));
+  }
+  auto result = [&]() {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    DeviceStager stager(input);
+    auto in = stager.to_comm(input).contiguous().variable_data();
+    auto& tr = tr_for(in);
+    const int P = tr.size();
+    TORCH_CHECK(in.size(axis) % P == 0,
+                "mpi4torch_amd: ReducescatterCompressed requires equal "
+                "counts: the axis size (", in.size(axis), ") must be a "
+                "multiple of the world size (", P, "); Reducescatter "
+                "handles variable counts");
+    debug_check_collective(group_name_, "ReducescatterCompressed", in, {axis});
+    auto outsizes = in.sizes().vec();
+    outsizes[axis] = in.size(axis) / P;
+    if (in.numel() == 0) {
+      return stager.from_comm(at::empty(outsizes, in.options()));
+    }
+    // World of one: nothing crosses a wire, so nothing is compressed — the
+    // result is an exact clone. force_full_path (GPU) runs the whole
+    // pipeline instead: quantize, self-exchange, mx8_reduce_to.
+    if (P == 1 && !(config().force_full_path && in.is_cuda())) {
+      return stager.from_comm(fast_clone(in));
+    }
+    const auto g = axis_geom(in, axis);
+    const int64_t count = g.axis / P;
+    const int64_t L = g.before * count * g.after;
+    Tensor packed = in.view({-1});
+    if (g.before != 1) {
+      // rank-major packing, exactly as Reducescatter does
+      packed = at::empty({(int64_t)P * L}, in.options());
+      std::vector<int64_t> counts(P, count);
+      auto displs = prefix_displs(counts);
+      std::vector<Tensor> blocks(P);
+      for (int p = 0; p < P; ++p) {
+        blocks[p] = packed.narrow(0, (int64_t)p * L, L);
+      }
+      move_axis_blocks(in, axis, displs, counts, blocks, /*pack=*/true);
+    }
+    return stager.from_comm(mx8_reducescatter(tr, packed, L).view(outsizes));
+  }();
+  attach_history(result, grad_fn);
+  return result;
+}
+
+// ---------------------------------------------------------------------------
 // Alltoall (reference csrc/extension.cpp:886-987). Unlike the reference's
 // composite of GetSize() successive Scatters (ref :940-981, which serializes
 // P collectives), this is ONE grouped RCCL p2p exchange with fused CDNA4
@@ -2713,6 +2872,38 @@ Tensor debug_mx8_dequantize(const Tensor& payload, const Tensor& scales,
                           current_gpu_stream(pay));
   } else {
     head.copy_(mx8_dequantize(pay, sc, numel, dtype));
+  }
+  return head;
+}
+
+Tensor debug_mx8_reduce_to(const Tensor& payload, const Tensor& scales,
+                           int64_t numel, at::ScalarType dtype,
+                           const c10::optional<Tensor>& out) {
+  TORCH_CHECK(payload.dim() == 2 && scales.dim() == 2 &&
+                  payload.scalar_type() == at::kByte &&
+                  scales.scalar_type() == at::kByte &&
+                  payload.size(0) == scales.size(0) && scales.size(0) >= 1 &&
+                  payload.size(1) == scales.size(1) * 32 && numel >= 0 &&
+                  (numel + 31) / 32 == scales.size(1),
+              "debug_mx8_reduce_to expects uint8 payload [P, G*32], scales "
+              "[P, G] and numel in (32*(G-1), 32*G]");
+  auto pin = payload.contiguous().view({-1});
+  auto sin = scales.contiguous().view({-1});
+  const int P = (int)scales.size(0);
+  if (!out.has_value()) return mx8_reduce_to(pin, sin, numel, P, dtype);
+  // write the first `numel` elements of a caller buffer (canary tests)
+  const Tensor& o = *out;
+  TORCH_CHECK(o.dim() == 1 && o.is_contiguous() && o.numel() >= numel &&
+                  o.scalar_type() == dtype && o.device() == pin.device(),
+              "debug_mx8_reduce_to: out must be a flat contiguous tensor "
+              "of the requested dtype with at least numel elements");
+  auto head = o.narrow(0, 0, numel);
+  if (pin.is_cuda()) {
+    launch_mx8_reduce_to(pin.data_ptr(), sin.data_ptr(), head.data_ptr(),
+                         numel, P, mx8_dtype_code(dtype),
+                         current_gpu_stream(pin));
+  } else {
+    head.copy_(mx8_reduce_to(pin, sin, numel, P, dtype));
   }
   return head;
 }

@@ -48,6 +48,15 @@ struct Communicator : torch::CustomClassHolder {
   // gradient/optimizer sharding (parallel/zero.py).
   at::Tensor Reducescatter(const at::Tensor& input, int64_t axis,
                            int64_t numelem);
+  // Sum reduce-scatter over the mxfp8 wire (MI355X extension): the axis is
+  // split into GetSize() equal blocks, each block is quantized once in
+  // groups of 32 that start at the block, block j travels to rank j, and
+  // the fused gfx950 tail sums the copies in fp32 straight into the input
+  // dtype (no requantization, no allgather: half the wire bytes of
+  // AllreduceCompressed). float32/bfloat16/float16 only; the axis size
+  // must be a multiple of the world size. Backward: uncompressed Allgather
+  // of the gradient. A world of one returns an exact clone.
+  at::Tensor ReducescatterCompressed(const at::Tensor& input, int64_t axis);
   at::Tensor Scatter(const at::Tensor& input, int64_t scatteraxis,
                      int64_t numelem, int64_t root);
   at::Tensor Alltoall(const at::Tensor& input, int64_t gatheraxis,
@@ -149,6 +158,12 @@ at::Tensor debug_mx8_dequantize(const at::Tensor& payload,
                                 const at::Tensor& scales, int64_t numel,
                                 at::ScalarType dtype,
                                 const c10::optional<at::Tensor>& out);
+// payload [P, G*32], scales [P, G] -> flat [numel] of dtype: the
+// reduce-scatter tail (fp32 rank-order sum, one cast, no requantization)
+at::Tensor debug_mx8_reduce_to(const at::Tensor& payload,
+                               const at::Tensor& scales, int64_t numel,
+                               at::ScalarType dtype,
+                               const c10::optional<at::Tensor>& out);
 // stacked: [nranks, ..., 2] (value, location) pairs; op: 0=minloc 1=maxloc
 at::Tensor debug_pairloc_reduce(const at::Tensor& stacked, int64_t op);
 

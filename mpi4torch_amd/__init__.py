@@ -210,6 +210,32 @@ class MPI_Communicator:
         primitive."""
         return self._comm.Reducescatter(tensor, axis, numelem)
 
+    def ReducescatterCompressed(self, tensor: torch.Tensor,
+                                axis: int = 0) -> torch.Tensor:
+        """Sum reduce-scatter that travels as block-scaled fp8 (MI355X
+        extension): the ZeRO-2 gradient primitive over the mxfp8 wire.
+
+        ``axis`` is split into ``size`` equal blocks (its length must be a
+        multiple of the world size; Reducescatter handles variable counts)
+        and this rank keeps block ``rank`` of the elementwise sum. Each
+        block of the tensor (float32, bfloat16 or float16) is quantized to
+        mxfp8 in groups of 32 consecutive elements that start at the
+        block's first element, block ``j`` travels to rank ``j``, and a
+        fused gfx950 kernel sums the copies in fp32, in rank order, straight
+        into the input dtype. Every value is quantized exactly once, the
+        sum is never requantized, and the wire carries half the bytes of
+        AllreduceCompressed (no allgather). A non-finite value turns the
+        group of 32 that holds it into NaN on the rank that owns it.
+
+        A world of one returns an exact clone: nothing crosses a wire, so
+        nothing is compressed.
+
+        Backward: Allgather of the gradient along ``axis`` — the exact
+        adjoint of the sum; quantization is straight-through and the
+        gradient travels uncompressed.
+        """
+        return self._comm.ReducescatterCompressed(tensor, axis)
+
     def Scatter(self, tensor: torch.Tensor, scatteraxis: int, numelem: int,
                 root: int) -> torch.Tensor:
         """Distribute ``root``'s tensor along ``scatteraxis``; this rank

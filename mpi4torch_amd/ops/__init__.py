@@ -58,6 +58,11 @@ def reducescatter(tensor: torch.Tensor, axis: int = 0, numelem: int = 1,
     return _comm(comm).Reducescatter(tensor, axis, numelem)
 
 
+def reducescatter_compressed(tensor: torch.Tensor, axis: int = 0, comm=None):
+    """Sum reduce-scatter over an mxfp8 wire (equal blocks along ``axis``)."""
+    return _comm(comm).ReducescatterCompressed(tensor, axis)
+
+
 def alltoallv(tensor: torch.Tensor, gatheraxis: int, scatteraxis: int,
               target_counts, source_sizes, comm=None):
     return _comm(comm).Alltoallv(tensor, gatheraxis, scatteraxis,

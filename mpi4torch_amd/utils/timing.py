@@ -35,6 +35,15 @@ def mxfp8_wire_bytes(numel: int) -> int:
     return 33 * ((numel + 31) // 32)
 
 
+def mxfp8_reducescatter_wire_bytes(numel: int, world: int) -> int:
+    """Bytes one rank sends in ReducescatterCompressed of ``numel`` elements
+    over ``world`` ranks: its copy of every other rank's block, each block
+    of numel/world elements quantized on its own (33 bytes per group of 32,
+    the partial last group padded). Half of the compressed allreduce."""
+    block = -(-numel // world)
+    return (world - 1) * 33 * ((block + 31) // 32)
+
+
 class CollectiveTimer:
     """Times GPU regions with CUDA/HIP events (no host sync until query)."""
 

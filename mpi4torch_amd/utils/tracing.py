@@ -129,6 +129,11 @@ class TracedCommunicator:
             "Reducescatter", tensor,
             lambda: self._comm.Reducescatter(tensor, axis, numelem))
 
+    def ReducescatterCompressed(self, tensor, axis=0):
+        return self._record(
+            "ReducescatterCompressed", tensor,
+            lambda: self._comm.ReducescatterCompressed(tensor, axis))
+
     def Alltoallv(self, tensor, gatheraxis, scatteraxis, target_counts,
                   source_sizes):
         return self._record(

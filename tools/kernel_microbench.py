@@ -6,10 +6,13 @@ Each kernel moves (nranks*N reads + N writes) or (N reads + N writes) —
 reported GB/s counts actual bytes touched. Run on an MI355X box:
     python tools/kernel_microbench.py            # everything
     python tools/kernel_microbench.py --mx8      # only the mxfp8 codec section
+    python tools/kernel_microbench.py --mx8-reduce-to   # only its last part
 
 The mxfp8 section times the three codec kernels and, in the same run and
 alternating with it, the sibling fp8_reduce kernel at the same P and n, so
-the ratio between the two is not a comparison across runs.
+the ratio between the two is not a comparison across runs. Its last part
+times the fused reduce-scatter tail mx8_reduce_to against the two-kernel
+sequence it replaces (mx8_reduce then mx8_dequantize), again alternating.
 """
 
 import os
@@ -122,8 +125,58 @@ def mx8_section(repeats=5):
     line("w1 full-path Allreduce", ta, t.numel() * 2)
 
 
+def mx8_reduce_to_section(repeats=5):
+    """mx8_reduce_to per output dtype at the reduce's shape (P = 8 copies of
+    n = 2Mi groups) against mx8_reduce + mx8_dequantize of the same block,
+    alternating in the same run. Bytes of the fused kernel: P*33n/32 in +
+    n*32*esize out (>= 656 MiB per launch, past the Infinity Cache); the
+    pair moves 33n/32 more out and in again."""
+    C = m._C
+    med = lambda v: sorted(v)[len(v) // 2]
+    n = N // 32
+    src = torch.randn(P, N, device="cuda") * 0.2
+    src.view(P, n, 32).mul_(torch.rand(P, n, 1, device="cuda"))
+    qs = [C._mx8_quantize(src[r]) for r in range(P)]
+    pay = torch.stack([q[0] for q in qs])
+    sc = torch.stack([q[1] for q in qs])
+    del src, qs
+
+    def line(name, times, nbytes):
+        t = med(times)
+        print(f"{name:34s} {t*1e3:9.1f} us  {nbytes/t/1e6:8.1f} GB/s  "
+              f"(min {min(times)*1e3:.1f} max {max(times)*1e3:.1f} us, "
+              f"{len(times)} repeats)", flush=True)
+        return t
+
+    def pair(dtype):
+        rp, rs = C._mx8_reduce(pay, sc)
+        return C._mx8_dequantize(rp, rs, N, dtype)
+
+    for dtype, tag in ((torch.float32, "fp32"), (torch.bfloat16, "bf16"),
+                       (torch.float16, "fp16")):
+        es = torch.empty(0, dtype=dtype).element_size()
+        t_pair, t_fused = [], []
+        for _ in range(repeats):
+            t_pair.append(timeit(lambda: pair(dtype)))
+            t_fused.append(timeit(lambda: C._mx8_reduce_to(pay, sc, N, dtype)))
+        fused_b = P * 33 * n + n * 32 * es
+        a = line(f"mx8_reduce+dequantize {tag} P={P}", t_pair,
+                 fused_b + 2 * 33 * n)
+        b = line(f"mx8_reduce_to {tag} P={P} n={n>>20}Mi grp", t_fused,
+                 fused_b)
+        spread = (max(t_pair) - min(t_pair)) / med(t_pair)
+        print(f"mx8_reduce_to / pair time ratio {tag} {b/a:.3f} "
+              f"(pair spread {spread*100:.1f}% of its median)", flush=True)
+
+
+if "--mx8-reduce-to" in sys.argv:
+    mx8_reduce_to_section()
+    dist.destroy_process_group()
+    sys.exit(0)
+
 if "--mx8" in sys.argv:
     mx8_section()
+    mx8_reduce_to_section()
     dist.destroy_process_group()
     sys.exit(0)
 
@@ -185,5 +238,6 @@ report(f"arith_reduce bf16 P={P} 128MiB", ms, (P + 1) * nb * 2)
 del own, stg
 
 mx8_section()
+mx8_reduce_to_section()
 
 dist.destroy_process_group()
