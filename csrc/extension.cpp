@@ -52,6 +52,7 @@ static auto communicator_class =
         .def("Reducescatter", &Communicator::Reducescatter)
         .def("ReducescatterCompressed",
              &Communicator::ReducescatterCompressed)
+        .def("AllgatherCompressed", &Communicator::AllgatherCompressed)
         .def("Scatter", &Communicator::Scatter)
         .def("Alltoall", &Communicator::Alltoall)
         .def("Alltoallv", &Communicator::Alltoallv)
@@ -105,6 +106,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
 
   m.def("_pack_roundtrip", &m4a::debug_pack_roundtrip);
   m.def("_slab_copy", &m4a::debug_slab_copy);
+  m.def("_unpack_blocks", &m4a::debug_unpack_blocks);
   m.def("_bitwise_reduce", &m4a::debug_bitwise_reduce);
   m.def("_fp8_reduce", &m4a::debug_fp8_reduce);
   m.def("_arith_reduce", &m4a::debug_arith_reduce);
@@ -116,6 +118,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out") = c10::optional<at::Tensor>());
   m.def("_mx8_reduce_to", &m4a::debug_mx8_reduce_to, py::arg("payload"),
         py::arg("scales"), py::arg("numel"), py::arg("dtype"),
+        py::arg("out") = c10::optional<at::Tensor>());
+  m.def("_mx8_dequantize_blocks", &m4a::debug_mx8_dequantize_blocks,
+        py::arg("payload"), py::arg("scales"), py::arg("rows"),
+        py::arg("row_elems"), py::arg("dtype"),
         py::arg("out") = c10::optional<at::Tensor>());
   m.def("reload_config", &m4a::reload_config_from_env);
 

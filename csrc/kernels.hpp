@@ -117,5 +117,16 @@ void launch_mx8_dequantize(const void* payload, const void* scales, void* out,
 void launch_mx8_reduce_to(const void* payload_in, const void* scales_in,
                           void* out, int64_t n_elems, int nranks, int dtype,
                           hipStream_t stream);
+// The allgather tail: nblocks mxfp8 streams, each of L = rows*row_elems
+// elements with groups that start at the block, dequantized straight into
+// place.
+// payload [nblocks][Gb*32], scales [nblocks][Gb], Gb = ceil(rows*row_elems/32)
+// out [rows][nblocks][row_elems] contiguous, of `dtype` (0=f32 1=bf16 2=f16):
+//   out[b][r][j] = cast(dq(block r))[b*row_elems + j]
+// Writes exactly rows*nblocks*row_elems elements. nblocks <= 65535 (grid.y).
+void launch_mx8_dequantize_blocks(const void* payload, const void* scales,
+                                  void* out, int nblocks, int64_t rows,
+                                  int64_t row_elems, int dtype,
+                                  hipStream_t stream);
 
 } // namespace m4a

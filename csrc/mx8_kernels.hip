@@ -14,7 +14,7 @@
 //     hardware RNE f32->e4m3 of hip_fp8.h, which cannot saturate because
 //     amax*2^-E <= 448 by construction.
 //
-// Four streaming kernels, all 256-thread workgroups, grid-stride, 16-byte
+// Five streaming kernels, all 256-thread workgroups, grid-stride, 16-byte
 // accesses on the wide side, nontemporal (every byte is touched once):
 //   quantize   : 8 lanes x 16 B per fp32 group, 4 lanes x 16 B per 16-bit
 //                group; amax crosses the lanes with 3 / 2 xor-shuffles;
@@ -29,9 +29,15 @@
 //                requantization: P copies summed in rank order straight
 //                into N elements of the output dtype, 32 output bytes per
 //                lane (two 16-byte stores).
-// Each has a one-thread-per-group scalar twin for base pointers that miss
-// the vector alignment (e.g. a contiguous x[1:] view); the partial last
-// group of the vector kernels goes through the same scalar group routine.
+//   dequantize_blocks : the allgather tail — the dequantize kernel's lane
+//                layout over P gathered blocks at once (grid.y = block),
+//                every 16-byte chunk stored straight at its place in the
+//                [rows][P][row_elems] output.
+// The first four have a one-thread-per-group scalar twin for base pointers
+// that miss the vector alignment (e.g. a contiguous x[1:] view); the partial
+// last group of their vector kernels goes through the same scalar group
+// routine. dequantize_blocks has a general twin that still stores aligned
+// 16-byte chunks (see there).
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp8.h>
@@ -568,6 +574,125 @@ __global__ __launch_bounds__(256) void mx8_reduce_to_kernel_scalar(
   }
 }
 
+// ---- dequantize_blocks (the allgather tail) ------------------------------
+//
+// nblocks mxfp8 streams of L = rows*row_elems elements each (groups start at
+// the block's first element): pay [nblocks][Gb*32], sc [nblocks][Gb],
+// Gb = ceil(L/32). Block r lands at out[:, r, :] of the contiguous
+// [rows][nblocks][row_elems] output. grid.y is the block, so the block is
+// wave-uniform and the only per-lane index arithmetic is chunk -> (row,
+// column): one division by the row length in 16-byte chunks, in 32 bits
+// whenever a block has fewer than 2^31 chunks (template parameter I).
+//
+// Vector body: the dequantize kernel's lane layout (4 or 8 payload bytes in,
+// one 16-byte store out) over ALL L/EPL chunks of the block. It requires
+// row_elems % EPL == 0, hence L % EPL == 0: every chunk lies inside one row
+// and the partial last group is made of whole chunks, so it needs no
+// separate tail and nothing past element L is written. Its payload bytes
+// exist because the payload is padded to Gb*32. The scale is indexed by the
+// block-flat group (chunk / LPG), never by the row, so a group may straddle
+// a row boundary.
+template <int K, typename I>
+__global__ __launch_bounds__(256) void mx8_dequantize_blocks_kernel(
+    const u8* __restrict__ pay, const u8* __restrict__ sc,
+    void* __restrict__ out, long long Gb, I chunks, I cpr,
+    long long nblocks) {
+  constexpr int LPG = K == kF32 ? 8 : 4;
+  constexpr int EPL = 32 / LPG;
+  const long long r = blockIdx.y;
+  const u8* __restrict__ bp = pay + r * Gb * 32;
+  const u8* __restrict__ bs = sc + r * Gb;
+  const I stride = (I)gridDim.x * blockDim.x;
+  for (I i = (I)blockIdx.x * blockDim.x + threadIdx.x; i < chunks;
+       i += stride) {
+    const int sb = bs[i / LPG];
+    unsigned w[EPL / 4];
+    if constexpr (K == kF32) {
+      w[0] = __builtin_nontemporal_load(
+          reinterpret_cast<const unsigned*>(bp) + i);
+    } else {
+      const v2u t =
+          __builtin_nontemporal_load(reinterpret_cast<const v2u*>(bp) + i);
+      w[0] = t[0];
+      w[EPL / 4 - 1] = t[1];
+    }
+    float x[EPL];
+    for (int d = 0; d < EPL / 4; ++d) {
+      for (int k = 0; k < 4; ++k) {
+        x[4 * d + k] = mx8_dequant((u8)(w[d] >> (8 * k)), sb);
+      }
+    }
+    const I row = i / cpr;
+    const I col = i - row * cpr;
+    const long long dst =
+        ((long long)row * nblocks + r) * (long long)cpr + (long long)col;
+    __builtin_nontemporal_store(pack16<K, EPL>(x),
+                                reinterpret_cast<v4u*>(out) + dst);
+  }
+}
+
+// General twin: any row length, any alignment of the payload and output
+// bases (an odd row_elems, a contiguous x[1:] view). A one-thread-per-group
+// twin like the siblings' would leave every store to single elements, and
+// the blocks of an odd-length allgather all start off 16 bytes. Instead
+// every (block, row) segment of row_elems elements is split at the 16-byte
+// boundaries of its DESTINATION: up to EPL-1 head elements, whole aligned
+// chunks, up to EPL-1 tail elements. Lane slots are flattened over (row,
+// slot) with row_elems/EPL + 2 slots per row: one per possible chunk, one
+// for the head and one for the tail, so rows of any length keep the lanes
+// busy; one division per lane maps the slot to its row. A chunk's EPL
+// payload bytes start at any byte (the compiler is free to load them
+// unaligned) and may belong to two groups, hence two scale bytes.
+template <int K, typename I>
+__global__ __launch_bounds__(256) void mx8_dequantize_blocks_kernel_shifted(
+    const u8* __restrict__ pay, const u8* __restrict__ sc,
+    void* __restrict__ out, long long Gb, long long row_elems, I slots,
+    I total, long long nblocks) {
+  using T = typename Elem<K>::type;
+  constexpr int EPL = K == kF32 ? 4 : 8;
+  const long long r = blockIdx.y;
+  const u8* __restrict__ bp = pay + r * Gb * 32;
+  const u8* __restrict__ bs = sc + r * Gb;
+  const I stride = (I)gridDim.x * blockDim.x;
+  for (I i = (I)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += stride) {
+    const I b = i / slots;
+    const long long k = (long long)(i - b * slots);
+    T* d = reinterpret_cast<T*>(out) +
+           ((long long)b * nblocks + r) * row_elems;  // the segment
+    const long long s0 = (long long)b * row_elems;    // its block-flat start
+    long long head =
+        (long long)(((16 - (reinterpret_cast<uintptr_t>(d) & 15)) & 15) /
+                    sizeof(T));
+    if (head > row_elems) head = row_elems;
+    const long long nchunks = (row_elems - head) / EPL;
+    if (k < nchunks) {
+      const long long e = head + k * EPL;
+      const long long src = s0 + e;
+      u8 pb[EPL];
+      __builtin_memcpy(pb, bp + src, EPL);
+      const long long g0 = src >> 5;
+      const int sb0 = bs[g0];
+      const int sb1 = bs[(src + EPL - 1) >> 5];
+      float x[EPL];
+      for (int t = 0; t < EPL; ++t) {
+        x[t] = mx8_dequant(pb[t], ((src + t) >> 5) == g0 ? sb0 : sb1);
+      }
+      __builtin_nontemporal_store(pack16<K, EPL>(x),
+                                  reinterpret_cast<v4u*>(d + e));
+    } else if (k >= (long long)slots - 2) {
+      // head [0, head) or tail [head + nchunks*EPL, row_elems): fewer than
+      // EPL elements each, stored one by one
+      const bool is_head = k == (long long)slots - 2;
+      const long long lo = is_head ? 0 : head + nchunks * EPL;
+      const long long hi = is_head ? head : row_elems;
+      for (long long e = lo; e < hi; ++e) {
+        d[e] = f32_to_elem<K>(mx8_dequant(bp[s0 + e], bs[(s0 + e) >> 5]));
+      }
+    }
+  }
+}
+
 inline unsigned grid_for(long long work) {
   long long blocks = (work + 255) / 256;
   if (blocks > 4096) blocks = 4096;
@@ -633,7 +758,77 @@ void launch_reduce_to_t(const u8* pin, const u8* sin, void* out, int64_t N,
   }
 }
 
+template <int K>
+void launch_dequantize_blocks_t(const u8* pay, const u8* sc, void* out,
+                                int nblocks, int64_t rows, int64_t row_elems,
+                                hipStream_t stream) {
+  constexpr int LPG = K == kF32 ? 8 : 4;
+  constexpr int EPL = 32 / LPG;
+  const long long L = rows * row_elems;
+  const long long Gb = (L + 31) / 32;
+  // Every block's payload base is pay + r*Gb*32, so an aligned pay keeps all
+  // of them aligned; row_elems % EPL == 0 with an aligned out keeps every
+  // chunk's destination aligned.
+  const bool al = aligned(out, 16) && aligned(pay, 32 / LPG);
+  if (al && rows == 1 && L % 32 == 0) {
+    // the gathered buffer is one flat mxfp8 stream of nblocks*L elements
+    launch_dequantize_t<K>(pay, sc, out, (int64_t)nblocks * L, stream);
+    return;
+  }
+  // grid.y carries the block; grid.x is capped so the launch stays near the
+  // 4096 workgroups of the siblings
+  const long long xcap = 4096 / nblocks > 0 ? 4096 / nblocks : 1;
+  auto grid = [&](long long work) {
+    long long x = (work + 255) / 256;
+    if (x > xcap) x = xcap;
+    if (x < 1) x = 1;
+    return dim3((unsigned)x, (unsigned)nblocks);
+  };
+  if (al && row_elems % EPL == 0) {
+    const long long chunks = L / EPL;
+    const long long cpr = row_elems / EPL;
+    if (chunks < (1ll << 31)) {
+      hipLaunchKernelGGL((mx8_dequantize_blocks_kernel<K, unsigned>),
+                         grid(chunks), dim3(256), 0, stream, pay, sc, out, Gb,
+                         (unsigned)chunks, (unsigned)cpr,
+                         (long long)nblocks);
+    } else {
+      hipLaunchKernelGGL((mx8_dequantize_blocks_kernel<K, long long>),
+                         grid(chunks), dim3(256), 0, stream, pay, sc, out, Gb,
+                         chunks, cpr, (long long)nblocks);
+    }
+  } else {
+    const long long slots = row_elems / EPL + 2;
+    const long long total = rows * slots;
+    if (total < (1ll << 31)) {
+      hipLaunchKernelGGL((mx8_dequantize_blocks_kernel_shifted<K, unsigned>),
+                         grid(total), dim3(256), 0, stream, pay, sc, out, Gb,
+                         (long long)row_elems, (unsigned)slots,
+                         (unsigned)total, (long long)nblocks);
+    } else {
+      hipLaunchKernelGGL((mx8_dequantize_blocks_kernel_shifted<K, long long>),
+                         grid(total), dim3(256), 0, stream, pay, sc, out, Gb,
+                         (long long)row_elems, slots, total,
+                         (long long)nblocks);
+    }
+  }
+}
+
 } // namespace
+
+void launch_mx8_dequantize_blocks(const void* payload, const void* scales,
+                                  void* out, int nblocks, int64_t rows,
+                                  int64_t row_elems, int dtype,
+                                  hipStream_t stream) {
+  if (nblocks <= 0 || rows <= 0 || row_elems <= 0) return;
+  const u8* pay = static_cast<const u8*>(payload);
+  const u8* sc = static_cast<const u8*>(scales);
+  switch (dtype) {
+    case 0: launch_dequantize_blocks_t<kF32>(pay, sc, out, nblocks, rows, row_elems, stream); break;
+    case 1: launch_dequantize_blocks_t<kBF16>(pay, sc, out, nblocks, rows, row_elems, stream); break;
+    default: launch_dequantize_blocks_t<kF16>(pay, sc, out, nblocks, rows, row_elems, stream); break;
+  }
+}
 
 void launch_mx8_reduce_to(const void* payload_in, const void* scales_in,
                           void* out, int64_t n_elems, int nranks, int dtype,

@@ -1024,6 +1024,62 @@ Tensor mx8_reducescatter(Transport& tr, const Tensor& packed, int64_t L) {
   return mx8_reduce_to(stg_pay, stg_sc, L, P, packed.scalar_type());
 }
 
+// P gathered blocks: pay [P * Gb*32], sc [P * Gb], Gb = ceil(L/32),
+// L = rows*row_elems, groups starting at each block (views ok) ->
+// [rows, P, row_elems] of `dtype`. The allgather tail, normative here:
+//   out[b, r, j] = dq(block r)[b*row_elems + j].to(dtype)
+// A 255 scale gives a NaN group in that block only.
+Tensor mx8_dequantize_blocks(const Tensor& pay, const Tensor& sc, int P,
+                             int64_t rows, int64_t row_elems,
+                             at::ScalarType dtype) {
+  const int dt = mx8_dtype_code(dtype);
+  TORCH_CHECK(P >= 1 && P <= 65535,
+              "mpi4torch_amd: mx8_dequantize_blocks supports 1..65535 "
+              "blocks, got ", P);
+  auto out = at::empty({rows, (int64_t)P, row_elems},
+                       pay.options().dtype(dtype));
+  if (out.numel() == 0) return out;
+  if (pay.is_cuda()) {
+    launch_mx8_dequantize_blocks(pay.data_ptr(), sc.data_ptr(),
+                                 out.data_ptr(), P, rows, row_elems, dt,
+                                 current_gpu_stream(pay));
+    return out;
+  }
+  const int64_t L = rows * row_elems;
+  const int64_t Gb = (L + 31) / 32;
+  auto pv = pay.view({P, Gb, 32});
+  auto sv = sc.view({P, Gb});
+  for (int r = 0; r < P; ++r) {
+    auto d = mx8_dequantize_groups(pv[r], sv[r]).view({-1});
+    out.select(1, r).copy_(
+        d.narrow(0, 0, L).to(dtype).view({rows, row_elems}));
+  }
+  return out;
+}
+
+// The allgather of the family: `in` is this rank's contiguous tensor seen as
+// [rows, row_elems] (rows = the dims before the gather axis). It is
+// quantized once as one flat stream (groups start at its first element),
+// payload and scales are allgathered as bytes (equal counts: the plain
+// collective on both transports, no grouped p2p) and the fused tail
+// dequantizes every block, the own one included, straight into
+// [rows, P, row_elems]. Every rank decodes the same bytes, so results are
+// identical across ranks. Staging is two byte buffers of ~33/32 * P*L; the
+// wire carries (P-1)*33*ceil(L/32) bytes received per rank.
+Tensor mx8_allgather(Transport& tr, const Tensor& in, int64_t rows,
+                     int64_t row_elems) {
+  const int P = tr.size();
+  const int64_t Gb = (rows * row_elems + 31) / 32;
+  auto q = mx8_quantize(in.view({-1}));
+  auto bopts = in.options().dtype(at::kByte);
+  auto all_pay = at::empty({(int64_t)P * Gb * 32}, bopts);
+  auto all_sc = at::empty({(int64_t)P * Gb}, bopts);
+  tr.allgather_equal(q.first, all_pay);
+  tr.allgather_equal(q.second, all_sc);
+  return mx8_dequantize_blocks(all_pay, all_sc, P, rows, row_elems,
+                               in.scalar_type());
+}
+
 // The mxfp8 sibling of hierarchical_allreduce: quantize once, exchange each
 // rank's copy of group-block j to rank j (payload and scales as two
 // contiguous pieces per peer in ONE grouped call), fused
@@ -1999,6 +2055,78 @@ Tensor Communicator::ReducescatterCompressed(const Tensor& input,
 }
 
 // ---------------------------------------------------------------------------
+// AllgatherCompressed (MI355X extension; not in the reference API)
+// ---------------------------------------------------------------------------
+
+namespace {
+struct AllgatherCompressedBackward : public M4ANode {
+  explicit AllgatherCompressedBackward(int64_t axis) : axis(axis) {}
+  std::string name() const override {
+    return "M4AAllgatherCompressedBackward";
+  }
+  variable_list apply(variable_list&& grads) override {
+    variable_list out(1);
+    if (should_compute_output(0)) {
+      // exact adjoint of the concatenation; quantization is
+      // straight-through, and the gradient itself travels compressed
+      out[0] = comm->ReducescatterCompressed(grads[0], axis);
+    }
+    return out;
+  }
+  int64_t axis;
+};
+} // namespace
+
+Tensor Communicator::AllgatherCompressed(const Tensor& input, int64_t axis) {
+  TORCH_CHECK(input.scalar_type() == at::kFloat ||
+                  input.scalar_type() == at::kBFloat16 ||
+                  input.scalar_type() == at::kHalf,
+              "mpi4torch_amd: AllgatherCompressed supports float32, "
+              "bfloat16 and float16 tensors, got ", input.scalar_type());
+  axis = at::maybe_wrap_dim(axis, input.dim());
+  std::shared_ptr<M4ANode> grad_fn;
+  if (torch::autograd::compute_requires_grad(input)) {
+    grad_fn = make_node<AllgatherCompressedBackward>(
+        c10::intrusive_ptr<Communicator>::unsafe_reclaim_from_nonowning(this),
+        axis);
+    grad_fn->set_next_edges(torch::autograd::collect_next_edges(input));
+  }
+  auto result = [&]() {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    DeviceStager stager(input);
+    auto in = stager.to_comm(input).contiguous().variable_data();
+    auto& tr = tr_for(in);
+    const int P = tr.size();
+    // World of one: nothing crosses a wire, so nothing is compressed — the
+    // result is an exact clone. force_full_path (GPU) runs the whole
+    // pipeline instead: quantize, 1-rank allgather, mx8_dequantize_blocks.
+    if (P == 1 && !(config().force_full_path && in.is_cuda())) {
+      return stager.from_comm(fast_clone(in));
+    }
+    debug_check_axis_collective(group_name_, "AllgatherCompressed", in,
+                                {axis}, {axis});
+    const auto g = axis_geom(in, axis);
+    auto counts = host_allgather_int64(group_name_, g.axis);
+    const bool equal = std::all_of(counts.begin(), counts.end(),
+                                   [&](int64_t c) { return c == counts[0]; });
+    TORCH_CHECK(equal,
+                "mpi4torch_amd: AllgatherCompressed requires equal counts: "
+                "every rank's tensor must have the same size on axis ", axis,
+                " (this rank has ", g.axis, "); Allgather handles variable "
+                "counts");
+    auto outsizes = in.sizes().vec();
+    outsizes[axis] = g.axis * P;
+    if (in.numel() == 0) {
+      return stager.from_comm(at::empty(outsizes, in.options()));
+    }
+    return stager.from_comm(
+        mx8_allgather(tr, in, g.before, g.axis * g.after).view(outsizes));
+  }();
+  attach_history(result, grad_fn);
+  return result;
+}
+
+// ---------------------------------------------------------------------------
 // Alltoall (reference csrc/extension.cpp:886-987). Unlike the reference's
 // composite of GetSize() successive Scatters (ref :940-981, which serializes
 // P collectives), this is ONE grouped RCCL p2p exchange with fused CDNA4
@@ -2715,6 +2843,30 @@ Tensor debug_pack_roundtrip(const Tensor& input, int64_t axis,
   return out;
 }
 
+// The unpack Allgather runs after an equal-count gather with before > 1:
+// staging holds P rank-major blocks of [rows, row_elems]; block r goes to
+// out[:, r, :] (one move_axis_blocks call, one slab-copy launch on GPU).
+void debug_unpack_blocks(const Tensor& staging, const Tensor& out) {
+  TORCH_CHECK(out.dim() == 3 && out.is_contiguous() && staging.dim() == 1 &&
+                  staging.is_contiguous() &&
+                  staging.numel() == out.numel() &&
+                  staging.scalar_type() == out.scalar_type() &&
+                  staging.device() == out.device(),
+              "debug_unpack_blocks expects flat staging [P*rows*row_elems] "
+              "and a contiguous out [rows, P, row_elems] of the same dtype "
+              "and device");
+  const int64_t rows = out.size(0), P = out.size(1), re = out.size(2);
+  if (out.numel() == 0) return;
+  auto full = out.view({rows, P * re});
+  std::vector<int64_t> counts((size_t)P, re);
+  auto displs = prefix_displs(counts);
+  std::vector<Tensor> blocks((size_t)P);
+  for (int64_t r = 0; r < P; ++r) {
+    blocks[(size_t)r] = staging.narrow(0, r * rows * re, rows * re);
+  }
+  move_axis_blocks(full, 1, displs, counts, blocks, /*pack=*/false);
+}
+
 // One launch_slab_copy call over caller-chosen descriptors (byte offsets
 // into two flat uint8 tensors). Every descriptor is bounds-checked on the
 // host before anything is launched, so a wrong test raises instead of
@@ -2904,6 +3056,47 @@ Tensor debug_mx8_reduce_to(const Tensor& payload, const Tensor& scales,
                          current_gpu_stream(pin));
   } else {
     head.copy_(mx8_reduce_to(pin, sin, numel, P, dtype));
+  }
+  return head;
+}
+
+Tensor debug_mx8_dequantize_blocks(const Tensor& payload,
+                                   const Tensor& scales, int64_t rows,
+                                   int64_t row_elems, at::ScalarType dtype,
+                                   const c10::optional<Tensor>& out) {
+  TORCH_CHECK(payload.dim() == 2 && scales.dim() == 2 &&
+                  payload.scalar_type() == at::kByte &&
+                  scales.scalar_type() == at::kByte &&
+                  payload.size(0) == scales.size(0) && scales.size(0) >= 1 &&
+                  scales.size(0) <= 65535 &&
+                  payload.size(1) == scales.size(1) * 32 && rows >= 1 &&
+                  row_elems >= 1 &&
+                  (rows * row_elems + 31) / 32 == scales.size(1),
+              "debug_mx8_dequantize_blocks expects uint8 payload [P, Gb*32], "
+              "scales [P, Gb] and rows*row_elems in (32*(Gb-1), 32*Gb]");
+  auto pin = payload.contiguous().view({-1});
+  auto sin = scales.contiguous().view({-1});
+  const int P = (int)scales.size(0);
+  if (!out.has_value()) {
+    return mx8_dequantize_blocks(pin, sin, P, rows, row_elems, dtype);
+  }
+  // write the first rows*P*row_elems elements of a caller buffer (canary
+  // tests)
+  const int64_t total = rows * P * row_elems;
+  const Tensor& o = *out;
+  TORCH_CHECK(o.dim() == 1 && o.is_contiguous() && o.numel() >= total &&
+                  o.scalar_type() == dtype && o.device() == pin.device(),
+              "debug_mx8_dequantize_blocks: out must be a flat contiguous "
+              "tensor of the requested dtype with at least rows*P*row_elems "
+              "elements");
+  auto head = o.narrow(0, 0, total).view({rows, (int64_t)P, row_elems});
+  if (pin.is_cuda()) {
+    launch_mx8_dequantize_blocks(pin.data_ptr(), sin.data_ptr(),
+                                 head.data_ptr(), P, rows, row_elems,
+                                 mx8_dtype_code(dtype),
+                                 current_gpu_stream(pin));
+  } else {
+    head.copy_(mx8_dequantize_blocks(pin, sin, P, rows, row_elems, dtype));
   }
   return head;
 }

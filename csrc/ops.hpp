@@ -57,6 +57,14 @@ struct Communicator : torch::CustomClassHolder {
   // must be a multiple of the world size. Backward: uncompressed Allgather
   // of the gradient. A world of one returns an exact clone.
   at::Tensor ReducescatterCompressed(const at::Tensor& input, int64_t axis);
+  // Allgather over the mxfp8 wire (MI355X extension): every rank's tensor
+  // (equal sizes on `axis`) is quantized once in groups of 32 that start at
+  // its first element, payload and scales are allgathered as bytes, and the
+  // fused gfx950 tail dequantizes every block — the own one included, so
+  // all ranks hold identical bytes — straight into its place along `axis`.
+  // float32/bfloat16/float16 only. Backward: ReducescatterCompressed of the
+  // gradient. A world of one returns an exact clone.
+  at::Tensor AllgatherCompressed(const at::Tensor& input, int64_t axis);
   at::Tensor Scatter(const at::Tensor& input, int64_t scatteraxis,
                      int64_t numelem, int64_t root);
   at::Tensor Alltoall(const at::Tensor& input, int64_t gatheraxis,
@@ -164,6 +172,17 @@ at::Tensor debug_mx8_reduce_to(const at::Tensor& payload,
                                const at::Tensor& scales, int64_t numel,
                                at::ScalarType dtype,
                                const c10::optional<at::Tensor>& out);
+// payload [P, Gb*32], scales [P, Gb], Gb = ceil(rows*row_elems/32) ->
+// [rows, P, row_elems] of dtype: the allgather tail (block r dequantized
+// into out[:, r, :])
+at::Tensor debug_mx8_dequantize_blocks(const at::Tensor& payload,
+                                       const at::Tensor& scales, int64_t rows,
+                                       int64_t row_elems,
+                                       at::ScalarType dtype,
+                                       const c10::optional<at::Tensor>& out);
+// staging: flat P rank-major blocks of [rows, row_elems]; out: contiguous
+// [rows, P, row_elems]. The axis unpack of an equal-count Allgather.
+void debug_unpack_blocks(const at::Tensor& staging, const at::Tensor& out);
 // stacked: [nranks, ..., 2] (value, location) pairs; op: 0=minloc 1=maxloc
 at::Tensor debug_pairloc_reduce(const at::Tensor& stacked, int64_t op);
 

@@ -236,6 +236,32 @@ class MPI_Communicator:
         """
         return self._comm.ReducescatterCompressed(tensor, axis)
 
+    def AllgatherCompressed(self, tensor: torch.Tensor,
+                            axis: int = 0) -> torch.Tensor:
+        """Allgather that travels as block-scaled fp8 (MI355X extension):
+        the FSDP parameter primitive over the mxfp8 wire.
+
+        Every rank's tensor (float32, bfloat16 or float16) must have the
+        same size on ``axis`` (Allgather handles variable counts); the
+        result holds rank ``r``'s tensor at block ``r`` along ``axis``.
+        Each rank quantizes its contiguous tensor once, in groups of 32
+        consecutive elements that start at its first element; payload and
+        scale bytes are allgathered, and a fused gfx950 kernel dequantizes
+        every block straight into its place in the input dtype. There is no
+        reduction, so every value is quantized exactly once. The own block
+        goes through the codec like every other: all ranks hold bit-identical
+        results. A non-finite value turns the group of 32 that holds it,
+        in its rank's block, into NaN.
+
+        A world of one returns an exact clone: nothing crosses a wire, so
+        nothing is compressed.
+
+        Backward: ReducescatterCompressed of the gradient along ``axis`` —
+        the exact adjoint of the concatenation; quantization is
+        straight-through and the gradient itself travels compressed.
+        """
+        return self._comm.AllgatherCompressed(tensor, axis)
+
     def Scatter(self, tensor: torch.Tensor, scatteraxis: int, numelem: int,
                 root: int) -> torch.Tensor:
         """Distribute ``root``'s tensor along ``scatteraxis``; this rank

@@ -63,6 +63,11 @@ def reducescatter_compressed(tensor: torch.Tensor, axis: int = 0, comm=None):
     return _comm(comm).ReducescatterCompressed(tensor, axis)
 
 
+def allgather_compressed(tensor: torch.Tensor, axis: int = 0, comm=None):
+    """Allgather over an mxfp8 wire (equal sizes along ``axis``)."""
+    return _comm(comm).AllgatherCompressed(tensor, axis)
+
+
 def alltoallv(tensor: torch.Tensor, gatheraxis: int, scatteraxis: int,
               target_counts, source_sizes, comm=None):
     return _comm(comm).Alltoallv(tensor, gatheraxis, scatteraxis,

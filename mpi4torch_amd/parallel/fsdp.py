@@ -18,6 +18,19 @@ Usage::
     loss = model(x).sum(); loss.backward()
     model.finish_backward()      # waits grad reduce-scatters
     opt.step(); model.refresh_shards()
+
+Compression (world > 1 only; a world of one runs no collective and
+compresses nothing): ``param_compression="mxfp8"`` gathers every unit's
+parameters with AllgatherCompressed (block-scaled fp8 wire, 33/32 byte per
+element). The master shard keeps full precision; every rank, the owner
+included, computes with the same dequantized parameters. That op is blocking
+(stream-ordered on GPU, host-blocking on gloo) and has no non-blocking
+variant, so nothing is prefetched for such a model: the gather happens in
+materialize(). ``grad_compression="mxfp8"`` reduces every unit's gradient
+with the blocking ReducescatterCompressed as soon as the unit's backward is
+done, in place of the non-blocking Ireducescatter; the reduced shard is kept
+until finish_backward(). Neither option changes shard_len, so sharded
+checkpoints stay interchangeable.
 """
 
 from typing import List, Optional, Sequence
@@ -28,9 +41,13 @@ import mpi4torch_amd as m4a
 
 
 class _Unit:
-    def __init__(self, module: torch.nn.Module, comm, master_dtype=None):
+    def __init__(self, module: torch.nn.Module, comm, master_dtype=None,
+                 param_compression: Optional[str] = None,
+                 grad_compression: Optional[str] = None):
         self.module = module
         self.comm = comm
+        self.param_compression = param_compression
+        self.grad_compression = grad_compression
         self.params: List[torch.nn.Parameter] = [
             p for p in module.parameters() if p.requires_grad
         ]
@@ -42,6 +59,13 @@ class _Unit:
         self.padded = self.shard_len * P
 
         p0 = self.params[0]
+        if ((param_compression is not None or grad_compression is not None)
+                and p0.dtype not in (torch.float32, torch.bfloat16,
+                                     torch.float16)):
+            raise ValueError(
+                "mpi4torch_amd FSDP: param_compression/grad_compression="
+                "'mxfp8' needs a float32, bfloat16 or float16 unit; this "
+                f"unit's flat buffer is {p0.dtype}")
         with torch.no_grad():
             flat = torch.zeros(self.padded, dtype=p0.dtype, device=p0.device)
             torch.cat([p.reshape(-1) for p in self.params], out=flat[:total])
@@ -60,6 +84,7 @@ class _Unit:
                 off += n
         self.materialized = True
         self.grad_handle = None
+        self.grad_reduced = None  # shard already reduced (compressed path)
         self.prefetch_handle = None
         self.pending = 0
 
@@ -73,9 +98,14 @@ class _Unit:
     def start_materialize(self):
         """Prefetch: launch this unit's parameter allgather without waiting
         (Iallgather skips the returning stream bracket), so it overlaps the
-        CURRENT unit's compute. materialize() consumes the handle."""
+        CURRENT unit's compute. materialize() consumes the handle.
+
+        With param_compression nothing is launched here: AllgatherCompressed
+        has no non-blocking variant, so the gather happens, blocking, in
+        materialize()."""
         if (self.materialized or self.prefetch_handle is not None
-                or self.comm.size == 1):
+                or self.comm.size == 1
+                or self.param_compression is not None):
             return
         local = self.shard.detach()
         if local.dtype != self.flat.dtype:
@@ -98,7 +128,10 @@ class _Unit:
         if local.dtype != self.flat.dtype:
             local = local.to(self.flat.dtype)  # model dtype on the wire
         if self.comm.size > 1:
-            full = self.comm.Allgather(local, 0)
+            # compressed: every rank, the owner included, gets dq(q(shard))
+            full = (self.comm.AllgatherCompressed(local, 0)
+                    if self.param_compression is not None
+                    else self.comm.Allgather(local, 0))
             self.flat.copy_(full)
         else:
             self.flat[:self.shard_len].copy_(local)
@@ -115,7 +148,10 @@ class _Unit:
                 gflat[off:off + n].copy_(p.grad.reshape(-1))
             p.grad = None
             off += n
-        if self.comm.size > 1:
+        if self.comm.size > 1 and self.grad_compression is not None:
+            # blocking: stream-ordered on GPU, host-blocking on gloo
+            self.grad_reduced = self.comm.ReducescatterCompressed(gflat, 0)
+        elif self.comm.size > 1:
             self.grad_handle = self.comm.Ireducescatter(gflat, m4a.MPI_SUM)
         else:
             self.shard.grad = (gflat[:self.shard_len].clone()
@@ -124,21 +160,33 @@ class _Unit:
 
     @torch.no_grad()
     def finish_grad_reduce(self, average: bool):
-        if self.grad_handle is not None:
-            g = self.comm.Wait(self.grad_handle)
+        if self.grad_handle is not None or self.grad_reduced is not None:
+            g = (self.comm.Wait(self.grad_handle)
+                 if self.grad_handle is not None else self.grad_reduced)
             if average:
                 g = g / self.comm.size
             self.shard.grad = (g.to(self.shard.dtype)
                                if g.dtype != self.shard.dtype else g)
             self.grad_handle = None
+            self.grad_reduced = None
 
 
 class FullyShardedDataParallel(torch.nn.Module):
     def __init__(self, module: torch.nn.Module,
                  units: Optional[Sequence[torch.nn.Module]] = None,
                  comm=None, average: bool = True, master_dtype=None,
-                 prefetch: int = 1):
+                 prefetch: int = 1,
+                 param_compression: Optional[str] = None,
+                 grad_compression: Optional[str] = None):
         super().__init__()
+        for opt, val in (("param_compression", param_compression),
+                         ("grad_compression", grad_compression)):
+            if val not in (None, "mxfp8"):
+                raise ValueError(
+                    f"mpi4torch_amd FSDP: {opt} must be None or 'mxfp8', "
+                    f"got {val!r}")
+        self.param_compression = param_compression
+        self.grad_compression = grad_compression
         self.module = module
         self.comm = comm if comm is not None else m4a.COMM_WORLD
         self.average = average
@@ -177,7 +225,8 @@ class FullyShardedDataParallel(torch.nn.Module):
                         "grouping the tied modules together."
                     )
                 seen[p] = name
-        self._units = [_Unit(m, self.comm, master_dtype)
+        self._units = [_Unit(m, self.comm, master_dtype, param_compression,
+                             grad_compression)
                        for m in unit_modules]
         self._by_module = {u.module: u for u in self._units}
         self._by_param = {p: u for u in self._units for p in u.params}
@@ -242,6 +291,7 @@ class FullyShardedDataParallel(torch.nn.Module):
         # DistributedDataParallel(find_unused_parameters=True))
         if self._sync_enabled:
             fired = any(u.grad_handle is not None or
+                        u.grad_reduced is not None or
                         (self.comm.size == 1 and u.shard.grad is not None)
                         for u in self._units)
             missing = sum(u.pending for u in self._units

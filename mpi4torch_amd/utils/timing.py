@@ -44,6 +44,14 @@ def mxfp8_reducescatter_wire_bytes(numel: int, world: int) -> int:
     return (world - 1) * 33 * ((block + 31) // 32)
 
 
+def mxfp8_allgather_wire_bytes(numel: int, world: int) -> int:
+    """Bytes one rank receives in AllgatherCompressed of its own tensor of
+    ``numel`` elements over ``world`` ranks: every other rank's tensor as
+    one mxfp8 stream (33 bytes per group of 32, the partial last group
+    padded)."""
+    return (world - 1) * 33 * ((numel + 31) // 32)
+
+
 class CollectiveTimer:
     """Times GPU regions with CUDA/HIP events (no host sync until query)."""
 

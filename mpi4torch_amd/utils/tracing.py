@@ -134,6 +134,11 @@ class TracedCommunicator:
             "ReducescatterCompressed", tensor,
             lambda: self._comm.ReducescatterCompressed(tensor, axis))
 
+    def AllgatherCompressed(self, tensor, axis=0):
+        return self._record(
+            "AllgatherCompressed", tensor,
+            lambda: self._comm.AllgatherCompressed(tensor, axis))
+
     def Alltoallv(self, tensor, gatheraxis, scatteraxis, target_counts,
                   source_sizes):
         return self._record(

@@ -6,13 +6,17 @@ Each kernel moves (nranks*N reads + N writes) or (N reads + N writes) —
 reported GB/s counts actual bytes touched. Run on an MI355X box:
     python tools/kernel_microbench.py            # everything
     python tools/kernel_microbench.py --mx8      # only the mxfp8 codec section
-    python tools/kernel_microbench.py --mx8-reduce-to   # only its last part
+    python tools/kernel_microbench.py --mx8-reduce-to   # only that part
+    python tools/kernel_microbench.py --mx8-dequantize-blocks   # only that part
 
 The mxfp8 section times the three codec kernels and, in the same run and
 alternating with it, the sibling fp8_reduce kernel at the same P and n, so
 the ratio between the two is not a comparison across runs. Its last part
 times the fused reduce-scatter tail mx8_reduce_to against the two-kernel
 sequence it replaces (mx8_reduce then mx8_dequantize), again alternating.
+The dequantize-blocks part does the same for the fused allgather tail
+mx8_dequantize_blocks against P x mx8_dequantize into staging plus the slab
+unpack that Allgather uses.
 """
 
 import os
@@ -169,14 +173,130 @@ def mx8_reduce_to_section(repeats=5):
               f"(pair spread {spread*100:.1f}% of its median)", flush=True)
 
 
+def mx8_dequantize_blocks_section(repeats=5):
+    """mx8_dequantize_blocks per output dtype at P = 8 blocks against the
+    sequence it replaces, alternating in the same run, for three geometries:
+      (a) rows = 1, L % 32 == 0: one flat stream; against ONE mx8_dequantize
+          over the same bytes (the fused launcher dispatches to that kernel);
+      (b) rows = 8, row_elems*esize % 16 == 0, row_elems % 32 != 0 (groups
+          straddle the rows, vector path); against P x mx8_dequantize into
+          staging and the axis unpack of Allgather (_unpack_blocks: one
+          move_axis_blocks call, one slab-copy launch);
+      (c) rows = 1, odd L (scalar twin); against P x mx8_dequantize written
+          straight to each block's place (one row needs no unpack; blocks
+          1..P-1 start off 16 bytes and take that kernel's scalar twin).
+    Every block holds ~32Mi elements, so one launch reads 264 MiB and writes
+    512 MiB (16-bit) or 1 GiB (fp32), past the 256 MiB Infinity Cache. Bytes
+    of the fused kernel: P*33*ceil(L/32) in + P*L*esize out; the sequence of
+    (b) writes and reads P*L*esize once more."""
+    C = m._C
+    med = lambda v: sorted(v)[len(v) // 2]
+
+    def line(name, times, nbytes):
+        t = med(times)
+        print(f"{name:40s} {t*1e3:9.1f} us  {nbytes/t/1e6:8.1f} GB/s  "
+              f"(min {min(times)*1e3:.1f} max {max(times)*1e3:.1f} us, "
+              f"{len(times)} repeats)", flush=True)
+        return t
+
+    def quantized(L):
+        Gb = (L + 31) // 32
+        pay = torch.empty(P, Gb * 32, dtype=torch.uint8, device="cuda")
+        sc = torch.empty(P, Gb, dtype=torch.uint8, device="cuda")
+        for r in range(P):
+            x = torch.randn(L, device="cuda") * 0.2
+            x.mul_(torch.rand(L, device="cuda"))
+            q = C._mx8_quantize(x)
+            pay[r].copy_(q[0])
+            sc[r].copy_(q[1])
+            del x, q
+        return pay, sc
+
+    base = 32 << 20
+    geoms = (("a", 1, base), ("b", 8, base // 8 + 8), ("c", 1, base + 1))
+    for tag_g, rows, row_elems in geoms:
+        L = rows * row_elems
+        Gb = (L + 31) // 32
+        pay, sc = quantized(L)
+        for dtype, tag in ((torch.float32, "fp32"), (torch.bfloat16, "bf16"),
+                           (torch.float16, "fp16")):
+            es = torch.empty(0, dtype=dtype).element_size()
+            out = torch.empty(P * L, dtype=dtype, device="cuda")
+            fused = lambda: C._mx8_dequantize_blocks(pay, sc, rows, row_elems,
+                                                     dtype, out=out)
+            fused_b = P * 33 * Gb + P * L * es
+            if tag_g == "a":
+                pf, sf = pay.view(-1), sc.view(-1)
+                seq = lambda: C._mx8_dequantize(pf, sf, P * L, dtype, out=out)
+                seq_b, seq_name = fused_b, "1 x mx8_dequantize"
+            elif tag_g == "b":
+                stage = torch.empty(P * L, dtype=dtype, device="cuda")
+                parts = [stage[r * L:(r + 1) * L] for r in range(P)]
+                out3 = out.view(rows, P, row_elems)
+
+                def seq():
+                    for r in range(P):
+                        C._mx8_dequantize(pay[r], sc[r], L, dtype,
+                                          out=parts[r])
+                    C._unpack_blocks(stage, out3)
+
+                seq_b = fused_b + 2 * P * L * es
+                seq_name = f"{P} x mx8_dequantize + unpack"
+            else:
+                parts = [out[r * L:(r + 1) * L] for r in range(P)]
+
+                def seq():
+                    for r in range(P):
+                        C._mx8_dequantize(pay[r], sc[r], L, dtype,
+                                          out=parts[r])
+
+                seq_b, seq_name = fused_b, f"{P} x mx8_dequantize in place"
+            t_seq, t_fused = [], []
+            for _ in range(repeats):
+                t_seq.append(timeit(seq))
+                t_fused.append(timeit(fused))
+            a = line(f"({tag_g}) {seq_name} {tag}", t_seq, seq_b)
+            b = line(f"({tag_g}) mx8_dequantize_blocks {tag} "
+                     f"{rows}x{row_elems}", t_fused, fused_b)
+            spread = (max(t_seq) - min(t_seq)) / med(t_seq)
+            print(f"({tag_g}) fused / sequence time ratio {tag} {b/a:.3f} "
+                  f"(sequence min-max spread {spread*100:.1f}% of its "
+                  f"median)", flush=True)
+            del out
+            if tag_g == "b":
+                del stage, parts, out3
+        del pay, sc
+
+    # informational: codec overhead of the full pipeline at world size 1 (no
+    # wire at this size: quantize + 1-rank allgather + fused tail)
+    t = torch.randn(128 << 20, device="cuda").to(torch.bfloat16)  # 256 MiB
+    comm = m.COMM_WORLD
+    C.force_full_path(True)
+    try:
+        tc = [timeit(lambda: comm.AllgatherCompressed(t, 0), iters=10)
+              for _ in range(3)]
+        ta = [timeit(lambda: comm.Allgather(t, 0), iters=10)
+              for _ in range(3)]
+    finally:
+        C.force_full_path(False)
+    line("w1 full-path AllgatherCompressed", tc, t.numel() * 2)
+    line("w1 full-path Allgather", ta, t.numel() * 2)
+
+
 if "--mx8-reduce-to" in sys.argv:
     mx8_reduce_to_section()
+    dist.destroy_process_group()
+    sys.exit(0)
+
+if "--mx8-dequantize-blocks" in sys.argv:
+    mx8_dequantize_blocks_section()
     dist.destroy_process_group()
     sys.exit(0)
 
 if "--mx8" in sys.argv:
     mx8_section()
     mx8_reduce_to_section()
+    mx8_dequantize_blocks_section()
     dist.destroy_process_group()
     sys.exit(0)
 
@@ -239,5 +359,6 @@ del own, stg
 
 mx8_section()
 mx8_reduce_to_section()
+mx8_dequantize_blocks_section()
 
 dist.destroy_process_group()
