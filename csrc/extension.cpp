@@ -53,6 +53,7 @@ static auto communicator_class =
         .def("ReducescatterCompressed",
              &Communicator::ReducescatterCompressed)
         .def("AllgatherCompressed", &Communicator::AllgatherCompressed)
+        .def("AlltoallCompressed", &Communicator::AlltoallCompressed)
         .def("Scatter", &Communicator::Scatter)
         .def("Alltoall", &Communicator::Alltoall)
         .def("Alltoallv", &Communicator::Alltoallv)
@@ -107,6 +108,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("_pack_roundtrip", &m4a::debug_pack_roundtrip);
   m.def("_slab_copy", &m4a::debug_slab_copy);
   m.def("_unpack_blocks", &m4a::debug_unpack_blocks);
+  m.def("_pack_blocks", &m4a::debug_pack_blocks);
   m.def("_bitwise_reduce", &m4a::debug_bitwise_reduce);
   m.def("_fp8_reduce", &m4a::debug_fp8_reduce);
   m.def("_arith_reduce", &m4a::debug_arith_reduce);
@@ -123,7 +125,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("payload"), py::arg("scales"), py::arg("rows"),
         py::arg("row_elems"), py::arg("dtype"),
         py::arg("out") = c10::optional<at::Tensor>());
-  m.def("reload_config", &m4a::reload_config_from_env);
+  m.def("_mx8_quantize_blocks", &m4a::debug_mx8_quantize_blocks,
+        py::arg("x"), py::arg("nblocks"), py::arg("rows"),
+        py::arg("row_elems"),
+        py::arg("payload_out") = c10::optional<at::Tensor>(),
+        py::arg("scales_out") = c10::optional<at::Tensor>());
+  m.def("reload_config",&m4a::reload_config_from_env);
 
   m.def("_rccl_version", []() {
     int v = 0;

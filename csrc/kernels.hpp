@@ -128,5 +128,16 @@ void launch_mx8_dequantize_blocks(const void* payload, const void* scales,
                                   void* out, int nblocks, int64_t rows,
                                   int64_t row_elems, int dtype,
                                   hipStream_t stream);
+// The all-to-all head, the mirror of the above on the send side: the
+// contiguous in [rows][nblocks][row_elems] of `dtype` is read in place and
+// block r, the stream of L = rows*row_elems elements in[b][r][j] in (b, j)
+// order, is quantized in groups of 32 that start at the block:
+//   payload [nblocks][Gb*32], scales [nblocks][Gb], Gb = ceil(L/32)
+// byte for byte what launch_mx8_quantize gives on a contiguous copy of each
+// block (zero-padded partial last group included). Writes exactly
+// nblocks*Gb*33 bytes. nblocks <= 65535 (grid.y).
+void launch_mx8_quantize_blocks(const void* in, void* payload, void* scales,
+                                int nblocks, int64_t rows, int64_t row_elems,
+                                int dtype, hipStream_t stream);
 
 } // namespace m4a

@@ -14,7 +14,7 @@
 //     hardware RNE f32->e4m3 of hip_fp8.h, which cannot saturate because
 //     amax*2^-E <= 448 by construction.
 //
-// Five streaming kernels, all 256-thread workgroups, grid-stride, 16-byte
+// Six streaming kernels, all 256-thread workgroups, grid-stride, 16-byte
 // accesses on the wide side, nontemporal (every byte is touched once):
 //   quantize   : 8 lanes x 16 B per fp32 group, 4 lanes x 16 B per 16-bit
 //                group; amax crosses the lanes with 3 / 2 xor-shuffles;
@@ -33,11 +33,16 @@
 //                layout over P gathered blocks at once (grid.y = block),
 //                every 16-byte chunk stored straight at its place in the
 //                [rows][P][row_elems] output.
+//   quantize_blocks : the all-to-all head, its mirror — the quantize
+//                kernel's lane layout over the P blocks of a
+//                [rows][P][row_elems] input read in place (grid.y = block),
+//                one mxfp8 stream per block out.
 // The first four have a one-thread-per-group scalar twin for base pointers
 // that miss the vector alignment (e.g. a contiguous x[1:] view); the partial
 // last group of their vector kernels goes through the same scalar group
 // routine. dequantize_blocks has a general twin that still stores aligned
-// 16-byte chunks (see there).
+// 16-byte chunks (see there); quantize_blocks has a one-thread-per-group twin
+// with element-wise index mapping.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp8.h>
@@ -693,6 +698,107 @@ __global__ __launch_bounds__(256) void mx8_dequantize_blocks_kernel_shifted(
   }
 }
 
+// ---- quantize_blocks (the all-to-all head) -------------------------------
+//
+// The mirror of dequantize_blocks on the send side: the contiguous
+// [rows][nblocks][row_elems] input is read in place and block r, the stream
+// of L = rows*row_elems elements in[b][r][j] in (b, j) order, leaves as
+// pay[r][Gb*32], sc[r][Gb], Gb = ceil(L/32), byte for byte what
+// mx8_quantize gives on a contiguous copy of the block. grid.y is the block.
+//
+// Vector body: the quantize kernel's lane layout (one 16-byte load in, 4 or
+// 8 payload bytes out, amax across LPG lanes) over ALL Gb*LPG lane slots of
+// the block, so the wave-uniform loop also covers the partial last group. It
+// requires row_elems % EPL == 0: every chunk lies inside one row and L is a
+// whole number of chunks. Slots past L/EPL load nothing, count as zeros in
+// the amax and store the zero padding of the payload, which exists because
+// the payload is padded to Gb*32. Groups run over the block-flat slot index,
+// never over the row, so a group may straddle a row boundary.
+template <int K, typename I>
+__global__ __launch_bounds__(256) void mx8_quantize_blocks_kernel(
+    const void* __restrict__ in, u8* __restrict__ pay, u8* __restrict__ sc,
+    long long Gb, I chunks, I cpr, I slots, long long nblocks) {
+  constexpr int LPG = K == kF32 ? 8 : 4;
+  constexpr int EPL = 32 / LPG;
+  const long long r = blockIdx.y;
+  u8* __restrict__ bp = pay + r * Gb * 32;
+  u8* __restrict__ bs = sc + r * Gb;
+  const I stride = (I)gridDim.x * blockDim.x;
+  const int lane = threadIdx.x & 63;
+  // wave-uniform trip count: the shuffles below need every lane present
+  for (I i0 = (I)blockIdx.x * blockDim.x + (threadIdx.x & ~63); i0 < slots;
+       i0 += stride) {
+    const I i = i0 + lane;
+    float x[EPL];
+    if (i < chunks) {
+      const I row = i / cpr;
+      const I col = i - row * cpr;
+      const long long src =
+          ((long long)row * nblocks + r) * (long long)cpr + (long long)col;
+      const v4u w =
+          __builtin_nontemporal_load(reinterpret_cast<const v4u*>(in) + src);
+      unpack16<K, EPL>(w, x);
+    } else {
+      for (int k = 0; k < EPL; ++k) x[k] = 0.0f;
+    }
+    unsigned a = amax_bits_of(x);
+    for (int m = 1; m < LPG; m <<= 1) {
+      const unsigned o = (unsigned)__shfl_xor((int)a, m);
+      a = o > a ? o : a;
+    }
+    int E;
+    const int sb = mx8_scale_byte(a, &E);
+    if (i < slots) {
+      if constexpr (K == kF32) {
+        const unsigned o = sb == 255 ? 0u : quant4(x[0], x[1], x[2], x[3], E);
+        __builtin_nontemporal_store(o, reinterpret_cast<unsigned*>(bp) + i);
+      } else {
+        v2u o;
+        o[0] = sb == 255 ? 0u : quant4(x[0], x[1], x[2], x[3], E);
+        o[1] = sb == 255
+                   ? 0u
+                   : quant4(x[EPL - 4], x[EPL - 3], x[EPL - 2], x[EPL - 1], E);
+        __builtin_nontemporal_store(o, reinterpret_cast<v2u*>(bp) + i);
+      }
+    }
+    store_scales<LPG>(bs, (long long)(i0 / LPG), Gb, sb, lane);
+  }
+}
+
+// General twin: any row length, any alignment of the input and payload
+// bases (an odd row_elems, a contiguous x[1:] view). One thread per group,
+// like the first four kernels' twins; the group's first element is mapped to
+// (row, column) with one division and the 32 elements are walked from there.
+template <int K>
+__global__ __launch_bounds__(256) void mx8_quantize_blocks_kernel_scalar(
+    const void* __restrict__ in, u8* __restrict__ pay, u8* __restrict__ sc,
+    long long Gb, long long L, long long row_elems, long long nblocks) {
+  using T = typename Elem<K>::type;
+  const long long r = blockIdx.y;
+  const T* __restrict__ src = reinterpret_cast<const T*>(in);
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < Gb;
+       g += stride) {
+    const long long e0 = g * 32;
+    long long row = e0 / row_elems;
+    long long col = e0 - row * row_elems;
+    const T* p = src + (row * nblocks + r) * row_elems;
+    float x[32];
+    for (int k = 0; k < 32; ++k) {
+      if (e0 + k < L) {
+        x[k] = elem_to_f32<K>(p[col]);
+        if (++col == row_elems) {
+          col = 0;
+          p += nblocks * row_elems;
+        }
+      } else {
+        x[k] = 0.0f;
+      }
+    }
+    encode_group_scalar(x, pay + (r * Gb + g) * 32, sc + r * Gb + g);
+  }
+}
+
 inline unsigned grid_for(long long work) {
   long long blocks = (work + 255) / 256;
   if (blocks > 4096) blocks = 4096;
@@ -814,7 +920,66 @@ void launch_dequantize_blocks_t(const u8* pay, const u8* sc, void* out,
   }
 }
 
+template <int K>
+void launch_quantize_blocks_t(const void* in, u8* pay, u8* sc, int nblocks,
+                              int64_t rows, int64_t row_elems,
+                              hipStream_t stream) {
+  constexpr int LPG = K == kF32 ? 8 : 4;
+  constexpr int EPL = 32 / LPG;
+  const long long L = rows * row_elems;
+  const long long Gb = (L + 31) / 32;
+  // Every block's payload base is pay + r*Gb*32, so an aligned pay keeps all
+  // of them aligned; row_elems % EPL == 0 with an aligned in keeps every
+  // chunk's source aligned.
+  const bool al = aligned(in, 16) && aligned(pay, 32 / LPG);
+  if (al && rows == 1 && L % 32 == 0) {
+    // the input is one flat stream of nblocks*L elements whose groups
+    // coincide with the blocks' groups
+    launch_quantize_t<K>(in, pay, sc, (int64_t)nblocks * L, stream);
+    return;
+  }
+  const long long xcap = 4096 / nblocks > 0 ? 4096 / nblocks : 1;
+  auto grid = [&](long long work) {
+    long long x = (work + 255) / 256;
+    if (x > xcap) x = xcap;
+    if (x < 1) x = 1;
+    return dim3((unsigned)x, (unsigned)nblocks);
+  };
+  if (al && row_elems % EPL == 0) {
+    const long long chunks = L / EPL;
+    const long long cpr = row_elems / EPL;
+    const long long slots = Gb * LPG;
+    if (slots < (1ll << 31)) {
+      hipLaunchKernelGGL((mx8_quantize_blocks_kernel<K, unsigned>),
+                         grid(slots), dim3(256), 0, stream, in, pay, sc, Gb,
+                         (unsigned)chunks, (unsigned)cpr, (unsigned)slots,
+                         (long long)nblocks);
+    } else {
+      hipLaunchKernelGGL((mx8_quantize_blocks_kernel<K, long long>),
+                         grid(slots), dim3(256), 0, stream, in, pay, sc, Gb,
+                         chunks, cpr, slots, (long long)nblocks);
+    }
+  } else {
+    hipLaunchKernelGGL((mx8_quantize_blocks_kernel_scalar<K>), grid(Gb),
+                       dim3(256), 0, stream, in, pay, sc, Gb, L,
+                       (long long)row_elems, (long long)nblocks);
+  }
+}
+
 } // namespace
+
+void launch_mx8_quantize_blocks(const void* in, void* payload, void* scales,
+                                int nblocks, int64_t rows, int64_t row_elems,
+                                int dtype, hipStream_t stream) {
+  if (nblocks <= 0 || rows <= 0 || row_elems <= 0) return;
+  u8* pay = static_cast<u8*>(payload);
+  u8* sc = static_cast<u8*>(scales);
+  switch (dtype) {
+    case 0: launch_quantize_blocks_t<kF32>(in, pay, sc, nblocks, rows, row_elems, stream); break;
+    case 1: launch_quantize_blocks_t<kBF16>(in, pay, sc, nblocks, rows, row_elems, stream); break;
+    default: launch_quantize_blocks_t<kF16>(in, pay, sc, nblocks, rows, row_elems, stream); break;
+  }
+}
 
 void launch_mx8_dequantize_blocks(const void* payload, const void* scales,
                                   void* out, int nblocks, int64_t rows,

@@ -1080,6 +1080,73 @@ Tensor mx8_allgather(Transport& tr, const Tensor& in, int64_t rows,
                                in.scalar_type());
 }
 
+// `in`: contiguous, rows*P*row_elems elements seen as [rows, P, row_elems]
+// -> (payload [P, Gb*32], scales [P, Gb]), Gb = ceil(rows*row_elems/32).
+// The all-to-all head, normative here: block p is mx8_quantize of the
+// contiguous copy of in[:, p, :], so its groups start at the block and its
+// partial last group is zero-padded.
+std::pair<Tensor, Tensor> mx8_quantize_blocks(const Tensor& in, int P,
+                                              int64_t rows,
+                                              int64_t row_elems) {
+  const int dt = mx8_dtype_code(in.scalar_type());
+  TORCH_CHECK(P >= 1 && P <= 65535,
+              "mpi4torch_amd: mx8_quantize_blocks supports 1..65535 "
+              "blocks, got ", P);
+  const int64_t Gb = (rows * row_elems + 31) / 32;
+  auto bopts = in.options().dtype(at::kByte);
+  auto pay = at::empty({(int64_t)P, Gb * 32}, bopts);
+  auto sc = at::empty({(int64_t)P, Gb}, bopts);
+  if (pay.numel() == 0) return {pay, sc};
+  if (in.is_cuda()) {
+    launch_mx8_quantize_blocks(in.data_ptr(), pay.data_ptr(), sc.data_ptr(),
+                               P, rows, row_elems, dt,
+                               current_gpu_stream(in));
+    return {pay, sc};
+  }
+  auto v = in.view({rows, (int64_t)P, row_elems});
+  for (int p = 0; p < P; ++p) {
+    auto q = mx8_quantize(v.select(1, p).contiguous().view({-1}));
+    pay[p].copy_(q.first);
+    sc[p].copy_(q.second);
+  }
+  return {pay, sc};
+}
+
+// The all-to-all of the family: `in` is this rank's contiguous tensor seen
+// as [rows_s, P, row_s] (rows_s = the dims before the scatter axis, row_s =
+// its share n of the scatter axis times the dims after it). Block p, what
+// rank p keeps, is quantized in place in groups of 32 that start at the
+// block; block p travels to rank p (payload and scales as two contiguous
+// pieces per peer in ONE grouped call, the call shape of mx8_reducescatter)
+// and the fused tail dequantizes the P received blocks, the own one
+// included, straight into [rows_g, P, row_g] (the block shape split at the
+// gather axis). No pack pass, no unpack pass, no per-block launch; every
+// value is quantized exactly once. Staging is two pairs of byte buffers of
+// ~33/32 * numel; the wire carries (P-1)*33*ceil(numel/P/32) bytes per rank.
+Tensor mx8_alltoall(Transport& tr, const Tensor& in, int64_t rows_s,
+                    int64_t row_s, int64_t rows_g, int64_t row_g) {
+  const int P = tr.size();
+  const int64_t Gb = (rows_s * row_s + 31) / 32;
+  auto q = mx8_quantize_blocks(in, P, rows_s, row_s);
+  auto pay = q.first.view({-1});
+  auto sc = q.second.view({-1});
+  auto bopts = in.options().dtype(at::kByte);
+  auto stg_pay = at::empty({(int64_t)P * Gb * 32}, bopts);
+  auto stg_sc = at::empty({(int64_t)P * Gb}, bopts);
+  std::vector<Tensor> sends(2 * P), recvs(2 * P);
+  std::vector<int> peers(2 * P);
+  for (int p = 0; p < P; ++p) {
+    sends[2 * p] = pay.narrow(0, (int64_t)p * Gb * 32, Gb * 32);
+    sends[2 * p + 1] = sc.narrow(0, (int64_t)p * Gb, Gb);
+    recvs[2 * p] = stg_pay.narrow(0, (int64_t)p * Gb * 32, Gb * 32);
+    recvs[2 * p + 1] = stg_sc.narrow(0, (int64_t)p * Gb, Gb);
+    peers[2 * p] = peers[2 * p + 1] = p;
+  }
+  tr.exchange(sends, peers, recvs, peers);
+  return mx8_dequantize_blocks(stg_pay, stg_sc, P, rows_g, row_g,
+                               in.scalar_type());
+}
+
 // The mxfp8 sibling of hierarchical_allreduce: quantize once, exchange each
 // rank's copy of group-block j to rank j (payload and scales as two
 // contiguous pieces per peer in ONE grouped call), fused
@@ -2127,6 +2194,104 @@ Tensor Communicator::AllgatherCompressed(const Tensor& input, int64_t axis) {
 }
 
 // ---------------------------------------------------------------------------
+// AlltoallCompressed (MI355X extension; not in the reference API)
+// ---------------------------------------------------------------------------
+
+namespace {
+struct AlltoallCompressedBackward : public M4ANode {
+  AlltoallCompressedBackward(int64_t gaxis, int64_t saxis)
+      : gaxis(gaxis), saxis(saxis) {}
+  std::string name() const override {
+    return "M4AAlltoallCompressedBackward";
+  }
+  variable_list apply(variable_list&& grads) override {
+    variable_list out(1);
+    if (should_compute_output(0)) {
+      // exact adjoint of the permutation: the axes swapped; quantization is
+      // straight-through, and the gradient itself travels compressed
+      out[0] = comm->AlltoallCompressed(grads[0], saxis, gaxis);
+    }
+    return out;
+  }
+  int64_t gaxis, saxis;
+};
+} // namespace
+
+Tensor Communicator::AlltoallCompressed(const Tensor& input,
+                                        int64_t gatheraxis,
+                                        int64_t scatteraxis) {
+  TORCH_CHECK(input.scalar_type() == at::kFloat ||
+                  input.scalar_type() == at::kBFloat16 ||
+                  input.scalar_type() == at::kHalf,
+              "mpi4torch_amd: AlltoallCompressed supports float32, "
+              "bfloat16 and float16 tensors, got ", input.scalar_type());
+  gatheraxis = at::maybe_wrap_dim(gatheraxis, input.dim());
+  scatteraxis = at::maybe_wrap_dim(scatteraxis, input.dim());
+  TORCH_CHECK(gatheraxis != scatteraxis,
+              "mpi4torch_amd: AlltoallCompressed requires two different "
+              "axes, got ", gatheraxis, " for both; Alltoall handles the "
+              "same-axis repartition");
+  std::shared_ptr<M4ANode> grad_fn;
+  if (torch::autograd::compute_requires_grad(input)) {
+    grad_fn = make_node<AlltoallCompressedBackward>(
+        c10::intrusive_ptr<Communicator>::unsafe_reclaim_from_nonowning(this),
+        gatheraxis, scatteraxis);
+    grad_fn->set_next_edges(torch::autograd::collect_next_edges(input));
+  }
+  auto result = [&]() {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    DeviceStager stager(input);
+    auto in = stager.to_comm(input).contiguous().variable_data();
+    auto& tr = tr_for(in);
+    const int P = tr.size();
+    TORCH_CHECK(in.size(scatteraxis) % P == 0,
+                "mpi4torch_amd: AlltoallCompressed requires equal counts: "
+                "the scatter-axis size (", in.size(scatteraxis), ") must be "
+                "a multiple of the world size (", P, "); Alltoall/Alltoallv "
+                "handle variable counts");
+    // World of one: nothing crosses a wire, so nothing is compressed — the
+    // result is an exact clone. force_full_path (GPU) runs the whole
+    // pipeline instead: mx8_quantize_blocks, self-exchange,
+    // mx8_dequantize_blocks.
+    if (P == 1 && !(config().force_full_path && in.is_cuda())) {
+      return stager.from_comm(fast_clone(in));
+    }
+    debug_check_axis_collective(group_name_, "AlltoallCompressed", in,
+                                {gatheraxis}, {gatheraxis, scatteraxis});
+    const int64_t g = in.size(gatheraxis);
+    auto counts = host_allgather_int64(group_name_, g);
+    const bool equal = std::all_of(counts.begin(), counts.end(),
+                                   [&](int64_t c) { return c == counts[0]; });
+    TORCH_CHECK(equal,
+                "mpi4torch_amd: AlltoallCompressed requires equal counts: "
+                "every rank's tensor must have the same size on the gather "
+                "axis ", gatheraxis, " (this rank has ", g, "); "
+                "Alltoall/Alltoallv handle variable counts");
+    const int64_t n = in.size(scatteraxis) / P;
+    auto outsizes = in.sizes().vec();
+    outsizes[scatteraxis] = n;
+    outsizes[gatheraxis] = g * P;
+    if (in.numel() == 0) {
+      return stager.from_comm(at::empty(outsizes, in.options()));
+    }
+    // send side: `in` as [before_s][P][n*after_s]; receive side: the block
+    // shape (scatter axis at n, gather axis at g) split at the gather axis
+    const auto gs = axis_geom(in, scatteraxis);
+    int64_t before_g = 1, after_g = 1;
+    for (int64_t d = 0; d < in.dim(); ++d) {
+      const int64_t sz = d == scatteraxis ? n : in.size(d);
+      if (d < gatheraxis) before_g *= sz;
+      if (d > gatheraxis) after_g *= sz;
+    }
+    return stager.from_comm(mx8_alltoall(tr, in, gs.before, n * gs.after,
+                                         before_g, g * after_g)
+                                .view(outsizes));
+  }();
+  attach_history(result, grad_fn);
+  return result;
+}
+
+// ---------------------------------------------------------------------------
 // Alltoall (reference csrc/extension.cpp:886-987). Unlike the reference's
 // composite of GetSize() successive Scatters (ref :940-981, which serializes
 // P collectives), this is ONE grouped RCCL p2p exchange with fused CDNA4
@@ -2867,6 +3032,29 @@ void debug_unpack_blocks(const Tensor& staging, const Tensor& out) {
   move_axis_blocks(full, 1, displs, counts, blocks, /*pack=*/false);
 }
 
+// The mirror: the rank-major axis pack of an equal-count Reducescatter or
+// Alltoall (the pass mx8_quantize_blocks makes unnecessary).
+void debug_pack_blocks(const Tensor& in, const Tensor& staging) {
+  TORCH_CHECK(in.dim() == 3 && in.is_contiguous() && staging.dim() == 1 &&
+                  staging.is_contiguous() &&
+                  staging.numel() == in.numel() &&
+                  staging.scalar_type() == in.scalar_type() &&
+                  staging.device() == in.device(),
+              "debug_pack_blocks expects a contiguous in [rows, P, row_elems] "
+              "and flat staging [P*rows*row_elems] of the same dtype and "
+              "device");
+  const int64_t rows = in.size(0), P = in.size(1), re = in.size(2);
+  if (in.numel() == 0) return;
+  auto full = in.view({rows, P * re});
+  std::vector<int64_t> counts((size_t)P, re);
+  auto displs = prefix_displs(counts);
+  std::vector<Tensor> blocks((size_t)P);
+  for (int64_t r = 0; r < P; ++r) {
+    blocks[(size_t)r] = staging.narrow(0, r * rows * re, rows * re);
+  }
+  move_axis_blocks(full, 1, displs, counts, blocks, /*pack=*/true);
+}
+
 // One launch_slab_copy call over caller-chosen descriptors (byte offsets
 // into two flat uint8 tensors). Every descriptor is bounds-checked on the
 // host before anything is launched, so a wrong test raises instead of
@@ -3099,6 +3287,51 @@ Tensor debug_mx8_dequantize_blocks(const Tensor& payload,
     head.copy_(mx8_dequantize_blocks(pin, sin, P, rows, row_elems, dtype));
   }
   return head;
+}
+
+std::tuple<Tensor, Tensor> debug_mx8_quantize_blocks(
+    const Tensor& x, int64_t nblocks, int64_t rows, int64_t row_elems,
+    const c10::optional<Tensor>& payload_out,
+    const c10::optional<Tensor>& scales_out) {
+  TORCH_CHECK(x.dim() == 1 && x.is_contiguous() && nblocks >= 1 &&
+                  nblocks <= 65535 && rows >= 1 && row_elems >= 1 &&
+                  x.numel() == rows * nblocks * row_elems,
+              "debug_mx8_quantize_blocks expects a flat contiguous tensor of "
+              "rows*nblocks*row_elems elements and 1..65535 blocks");
+  TORCH_CHECK(payload_out.has_value() == scales_out.has_value(),
+              "debug_mx8_quantize_blocks: payload_out and scales_out go "
+              "together");
+  const int P = (int)nblocks;
+  if (!payload_out.has_value()) {
+    auto ps = mx8_quantize_blocks(x, P, rows, row_elems);
+    return std::make_tuple(ps.first, ps.second);
+  }
+  // write the heads of caller buffers (canary tests)
+  const int64_t Gb = (rows * row_elems + 31) / 32;
+  const Tensor& po = *payload_out;
+  const Tensor& so = *scales_out;
+  TORCH_CHECK(po.dim() == 1 && po.is_contiguous() &&
+                  po.scalar_type() == at::kByte &&
+                  po.numel() >= nblocks * Gb * 32 &&
+                  po.device() == x.device() && so.dim() == 1 &&
+                  so.is_contiguous() && so.scalar_type() == at::kByte &&
+                  so.numel() >= nblocks * Gb && so.device() == x.device(),
+              "debug_mx8_quantize_blocks: payload_out and scales_out must be "
+              "flat contiguous uint8 tensors with at least P*Gb*32 and P*Gb "
+              "elements");
+  auto ph = po.narrow(0, 0, nblocks * Gb * 32).view({nblocks, Gb * 32});
+  auto sh = so.narrow(0, 0, nblocks * Gb).view({nblocks, Gb});
+  if (x.is_cuda()) {
+    launch_mx8_quantize_blocks(x.data_ptr(), ph.data_ptr(), sh.data_ptr(), P,
+                               rows, row_elems,
+                               mx8_dtype_code(x.scalar_type()),
+                               current_gpu_stream(x));
+  } else {
+    auto ps = mx8_quantize_blocks(x, P, rows, row_elems);
+    ph.copy_(ps.first);
+    sh.copy_(ps.second);
+  }
+  return std::make_tuple(ph, sh);
 }
 
 Tensor debug_pairloc_reduce(const Tensor& stacked, int64_t op) {

@@ -65,6 +65,18 @@ struct Communicator : torch::CustomClassHolder {
   // float32/bfloat16/float16 only. Backward: ReducescatterCompressed of the
   // gradient. A world of one returns an exact clone.
   at::Tensor AllgatherCompressed(const at::Tensor& input, int64_t axis);
+  // Equal-count, two-axis all-to-all over the mxfp8 wire (MI355X
+  // extension): the scatter axis is split into GetSize() equal blocks, a
+  // fused gfx950 kernel quantizes every block in place (groups of 32 that
+  // start at the block), block j travels to rank j in one grouped
+  // exchange, and the fused tail dequantizes the received blocks, the own
+  // one included, straight into place along the gather axis (equal sizes
+  // on every rank). No pack or unpack pass; every value is quantized
+  // exactly once. float32/bfloat16/float16 only; the two axes must differ.
+  // Backward: AlltoallCompressed of the gradient with the axes swapped. A
+  // world of one returns an exact clone.
+  at::Tensor AlltoallCompressed(const at::Tensor& input, int64_t gatheraxis,
+                                int64_t scatteraxis);
   at::Tensor Scatter(const at::Tensor& input, int64_t scatteraxis,
                      int64_t numelem, int64_t root);
   at::Tensor Alltoall(const at::Tensor& input, int64_t gatheraxis,
@@ -180,9 +192,20 @@ at::Tensor debug_mx8_dequantize_blocks(const at::Tensor& payload,
                                        int64_t row_elems,
                                        at::ScalarType dtype,
                                        const c10::optional<at::Tensor>& out);
+// flat contiguous x of rows*nblocks*row_elems elements seen as
+// [rows, nblocks, row_elems] -> (payload [P, Gb*32], scales [P, Gb]): the
+// all-to-all head (block p = mx8_quantize of the contiguous x[:, p, :]).
+// With payload_out / scales_out (flat uint8) the results alias their heads.
+std::tuple<at::Tensor, at::Tensor> debug_mx8_quantize_blocks(
+    const at::Tensor& x, int64_t nblocks, int64_t rows, int64_t row_elems,
+    const c10::optional<at::Tensor>& payload_out,
+    const c10::optional<at::Tensor>& scales_out);
 // staging: flat P rank-major blocks of [rows, row_elems]; out: contiguous
 // [rows, P, row_elems]. The axis unpack of an equal-count Allgather.
 void debug_unpack_blocks(const at::Tensor& staging, const at::Tensor& out);
+// in: contiguous [rows, P, row_elems]; staging: flat P rank-major blocks of
+// [rows, row_elems]. The axis pack of an equal-count Reducescatter.
+void debug_pack_blocks(const at::Tensor& in, const at::Tensor& staging);
 // stacked: [nranks, ..., 2] (value, location) pairs; op: 0=minloc 1=maxloc
 at::Tensor debug_pairloc_reduce(const at::Tensor& stacked, int64_t op);
 

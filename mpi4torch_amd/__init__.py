@@ -262,6 +262,38 @@ class MPI_Communicator:
         """
         return self._comm.AllgatherCompressed(tensor, axis)
 
+    def AlltoallCompressed(self, tensor: torch.Tensor, gatheraxis: int,
+                           scatteraxis: int) -> torch.Tensor:
+        """Equal-count, two-axis all-to-all that travels as block-scaled
+        fp8 (MI355X extension): the Ulysses reshard primitive over the
+        mxfp8 wire.
+
+        ``scatteraxis`` is split into ``size`` equal blocks (its length must
+        be a multiple of the world size) and block ``j`` goes to rank ``j``;
+        the blocks this rank receives are concatenated along ``gatheraxis``
+        in rank order (every rank's tensor must have the same size there).
+        The two axes must differ; Alltoall/Alltoallv handle variable counts
+        and the same-axis repartition. Each block of the tensor (float32,
+        bfloat16 or float16) is quantized to mxfp8 in place by a fused
+        gfx950 kernel, in groups of 32 consecutive elements of the
+        contiguous block that start at its first element; payload and scale
+        bytes travel in one grouped exchange, and a second fused kernel
+        dequantizes the received blocks straight into place. There is no
+        pack or unpack pass and no reduction, so every value is quantized
+        exactly once. The own block goes through the codec like every
+        other. The wire carries 33 bytes per 32 elements: 33/64 of a
+        bfloat16 tensor, 33/128 of a float32 one. A non-finite value turns
+        the group of 32 that holds it into NaN on the rank that receives it.
+
+        A world of one returns an exact clone: nothing crosses a wire, so
+        nothing is compressed.
+
+        Backward: AlltoallCompressed of the gradient with the axes swapped —
+        the exact adjoint of the permutation; quantization is
+        straight-through and the gradient itself travels compressed.
+        """
+        return self._comm.AlltoallCompressed(tensor, gatheraxis, scatteraxis)
+
     def Scatter(self, tensor: torch.Tensor, scatteraxis: int, numelem: int,
                 root: int) -> torch.Tensor:
         """Distribute ``root``'s tensor along ``scatteraxis``; this rank

@@ -68,6 +68,12 @@ def allgather_compressed(tensor: torch.Tensor, axis: int = 0, comm=None):
     return _comm(comm).AllgatherCompressed(tensor, axis)
 
 
+def alltoall_compressed(tensor: torch.Tensor, gatheraxis: int,
+                        scatteraxis: int, comm=None):
+    """Equal-count two-axis all-to-all over an mxfp8 wire."""
+    return _comm(comm).AlltoallCompressed(tensor, gatheraxis, scatteraxis)
+
+
 def alltoallv(tensor: torch.Tensor, gatheraxis: int, scatteraxis: int,
               target_counts, source_sizes, comm=None):
     return _comm(comm).Alltoallv(tensor, gatheraxis, scatteraxis,

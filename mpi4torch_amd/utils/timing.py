@@ -52,6 +52,15 @@ def mxfp8_allgather_wire_bytes(numel: int, world: int) -> int:
     return (world - 1) * 33 * ((numel + 31) // 32)
 
 
+def alltoall_compressed_wire_bytes(numel: int, world: int) -> int:
+    """Bytes one rank sends in AlltoallCompressed of its own tensor of
+    ``numel`` elements over ``world`` ranks: every other rank's block of
+    numel/world elements, each quantized on its own (33 bytes per group of
+    32, the partial last group padded)."""
+    block = -(-numel // world)
+    return (world - 1) * 33 * ((block + 31) // 32)
+
+
 class CollectiveTimer:
     """Times GPU regions with CUDA/HIP events (no host sync until query)."""
 

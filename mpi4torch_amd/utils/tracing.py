@@ -139,6 +139,12 @@ class TracedCommunicator:
             "AllgatherCompressed", tensor,
             lambda: self._comm.AllgatherCompressed(tensor, axis))
 
+    def AlltoallCompressed(self, tensor, gatheraxis, scatteraxis):
+        return self._record(
+            "AlltoallCompressed", tensor,
+            lambda: self._comm.AlltoallCompressed(tensor, gatheraxis,
+                                                  scatteraxis))
+
     def Alltoallv(self, tensor, gatheraxis, scatteraxis, target_counts,
                   source_sizes):
         return self._record(

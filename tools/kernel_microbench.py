@@ -8,6 +8,7 @@ reported GB/s counts actual bytes touched. Run on an MI355X box:
     python tools/kernel_microbench.py --mx8      # only the mxfp8 codec section
     python tools/kernel_microbench.py --mx8-reduce-to   # only that part
     python tools/kernel_microbench.py --mx8-dequantize-blocks   # only that part
+    python tools/kernel_microbench.py --mx8-quantize-blocks     # only that part
 
 The mxfp8 section times the three codec kernels and, in the same run and
 alternating with it, the sibling fp8_reduce kernel at the same P and n, so
@@ -16,7 +17,9 @@ times the fused reduce-scatter tail mx8_reduce_to against the two-kernel
 sequence it replaces (mx8_reduce then mx8_dequantize), again alternating.
 The dequantize-blocks part does the same for the fused allgather tail
 mx8_dequantize_blocks against P x mx8_dequantize into staging plus the slab
-unpack that Allgather uses.
+unpack that Allgather uses. The quantize-blocks part does the same for the
+fused all-to-all head mx8_quantize_blocks against the axis pack into staging
+plus mx8_quantize.
 """
 
 import os
@@ -283,6 +286,108 @@ def mx8_dequantize_blocks_section(repeats=5):
     line("w1 full-path Allgather", ta, t.numel() * 2)
 
 
+def mx8_quantize_blocks_section(repeats=5):
+    """mx8_quantize_blocks per input dtype at P = 8 blocks against the
+    sequence it replaces, alternating in the same run, for four geometries:
+      (a)  rows = 1, L % 32 == 0: the input is one flat stream; against ONE
+           mx8_quantize over the same bytes (the fused launcher dispatches
+           to that kernel);
+      (b)  rows = 8, row_elems = 4Mi+8 (groups straddle the rows, vector
+           path); against the rank-major axis pack that ReducescatterCompressed
+           uses (_pack_blocks: one move_axis_blocks call, one slab-copy
+           launch) and ONE flat mx8_quantize of the staging (L % 32 == 0);
+      (b') rows = 32768, row_elems = 1024: the Ulysses shape with short
+           rows; against the same sequence;
+      (c)  rows = 1, odd L (general twin); against P x mx8_quantize of the
+           blocks in place (blocks 1..P-1 start off 16 bytes and take that
+           kernel's scalar twin).
+    Every block holds ~32Mi elements, so one launch reads 512 MiB (16-bit)
+    or 1 GiB (fp32) and writes 264 MiB, past the 256 MiB Infinity Cache.
+    Bytes of the fused kernel: P*L*esize in + P*33*ceil(L/32) out; the
+    sequence of (b)/(b') writes and reads P*L*esize once more."""
+    C = m._C
+    med = lambda v: sorted(v)[len(v) // 2]
+
+    def line(name, times, nbytes):
+        t = med(times)
+        print(f"{name:40s} {t*1e3:9.1f} us  {nbytes/t/1e6:8.1f} GB/s  "
+              f"(min {min(times)*1e3:.1f} max {max(times)*1e3:.1f} us, "
+              f"{len(times)} repeats)", flush=True)
+        return t
+
+    base = 32 << 20
+    geoms = (("a", 1, base), ("b", 8, base // 8 + 8),
+             ("b'", 32768, 1024), ("c", 1, base + 1))
+    for tag_g, rows, row_elems in geoms:
+        L = rows * row_elems
+        Gb = (L + 31) // 32
+        for dtype, tag in ((torch.float32, "fp32"), (torch.bfloat16, "bf16"),
+                           (torch.float16, "fp16")):
+            x = torch.randn(P * L, device="cuda") * 0.2
+            x.mul_(torch.rand(P * L, device="cuda"))
+            x = x.to(dtype)
+            es = x.element_size()
+            fused = lambda: C._mx8_quantize_blocks(x, P, rows, row_elems)
+            fused_b = P * L * es + P * 33 * Gb
+            if tag_g == "a":
+                seq = lambda: C._mx8_quantize(x)
+                seq_b, seq_name = fused_b, "1 x mx8_quantize"
+            elif tag_g in ("b", "b'"):
+                stage = torch.empty(P * L, dtype=dtype, device="cuda")
+                x3 = x.view(rows, P, row_elems)
+
+                def seq():
+                    C._pack_blocks(x3, stage)
+                    return C._mx8_quantize(stage)
+
+                seq_b = fused_b + 2 * P * L * es
+                seq_name = "pack + 1 x mx8_quantize"
+            else:
+                parts = [x[r * L:(r + 1) * L] for r in range(P)]
+
+                def seq():
+                    for r in range(P):
+                        C._mx8_quantize(parts[r])
+
+                seq_b, seq_name = fused_b, f"{P} x mx8_quantize in place"
+            t_seq, t_fused = [], []
+            for _ in range(repeats):
+                t_seq.append(timeit(seq))
+                t_fused.append(timeit(fused))
+            a = line(f"({tag_g}) {seq_name} {tag}", t_seq, seq_b)
+            b = line(f"({tag_g}) mx8_quantize_blocks {tag} "
+                     f"{rows}x{row_elems}", t_fused, fused_b)
+            spread = (max(t_seq) - min(t_seq)) / med(t_seq)
+            print(f"({tag_g}) fused / sequence time ratio {tag} {b/a:.3f} "
+                  f"(sequence min-max spread {spread*100:.1f}% of its "
+                  f"median; fused min-max {min(t_fused)*1e3:.1f}-"
+                  f"{max(t_fused)*1e3:.1f} us)", flush=True)
+            if tag_g in ("b", "b'"):
+                del stage, x3
+            del x
+
+    # informational: codec and staging overhead of the full pipeline at
+    # world size 1 (no wire at this size: fused head + self-exchange + fused
+    # tail) on the Ulysses-like [rows, heads*dim] reshard of 256 MiB bf16
+    t = torch.randn(32768, 4096, device="cuda").to(torch.bfloat16)
+    comm = m.COMM_WORLD
+    C.force_full_path(True)
+    try:
+        tc = [timeit(lambda: comm.AlltoallCompressed(t, 0, 1), iters=10)
+              for _ in range(3)]
+        ta = [timeit(lambda: comm.Alltoall(t, 0, 1, t.size(1)), iters=10)
+              for _ in range(3)]
+    finally:
+        C.force_full_path(False)
+    line("w1 full-path AlltoallCompressed", tc, t.numel() * 2)
+    line("w1 full-path Alltoall", ta, t.numel() * 2)
+
+
+if "--mx8-quantize-blocks" in sys.argv:
+    mx8_quantize_blocks_section()
+    dist.destroy_process_group()
+    sys.exit(0)
+
 if "--mx8-reduce-to" in sys.argv:
     mx8_reduce_to_section()
     dist.destroy_process_group()
@@ -297,6 +402,7 @@ if "--mx8" in sys.argv:
     mx8_section()
     mx8_reduce_to_section()
     mx8_dequantize_blocks_section()
+    mx8_quantize_blocks_section()
     dist.destroy_process_group()
     sys.exit(0)
 
@@ -360,5 +466,6 @@ del own, stg
 mx8_section()
 mx8_reduce_to_section()
 mx8_dequantize_blocks_section()
+mx8_quantize_blocks_section()
 
 dist.destroy_process_group()
