@@ -58,6 +58,8 @@ static auto communicator_class =
         .def("Alltoall", &Communicator::Alltoall)
         .def("Alltoallv", &Communicator::Alltoallv)
         .def("AlltoallPairwise", &Communicator::AlltoallPairwise)
+        .def("AlltoallPairwiseCompressed",
+             &Communicator::AlltoallPairwiseCompressed)
         .def("Iallreduce", &Communicator::Iallreduce)
         .def("Ireducescatter", &Communicator::Ireducescatter)
         .def("Iallgather", &Communicator::Iallgather)
@@ -130,6 +132,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("row_elems"),
         py::arg("payload_out") = c10::optional<at::Tensor>(),
         py::arg("scales_out") = c10::optional<at::Tensor>());
+  m.def("_mx8_quantize_segments", &m4a::debug_mx8_quantize_segments,
+        py::arg("x"), py::arg("rows"), py::arg("after"), py::arg("counts"),
+        py::arg("order") = c10::optional<at::Tensor>(),
+        py::arg("payload_out") = c10::optional<at::Tensor>(),
+        py::arg("scales_out") = c10::optional<at::Tensor>());
+  m.def("_mx8_dequantize_segments", &m4a::debug_mx8_dequantize_segments,
+        py::arg("payload"), py::arg("scales"), py::arg("rows"),
+        py::arg("after"), py::arg("counts"), py::arg("dtype"),
+        py::arg("order") = c10::optional<at::Tensor>(),
+        py::arg("out") = c10::optional<at::Tensor>());
+  m.attr("_MX8_MAX_SEGS_PER_LAUNCH") = (int64_t)m4a::kMaxMx8SegsPerLaunch;
   m.def("reload_config",&m4a::reload_config_from_env);
 
   m.def("_rccl_version", []() {

@@ -140,4 +140,44 @@ void launch_mx8_quantize_blocks(const void* in, void* payload, void* scales,
                                 int nblocks, int64_t rows, int64_t row_elems,
                                 int dtype, hipStream_t stream);
 
+// One segment of the variable-count codec kernels below: `count` slices of
+// the stream side starting at slice `displ`, whose mxfp8 stream starts at
+// group `goff` (payload byte 32*goff, scale byte goff).
+struct Mx8SegDesc {
+  int64_t displ;
+  int64_t count;
+  int64_t goff;
+};
+
+// Max segments handled by a single launch of the segments kernels (the
+// descriptors are passed by value in the kernel arguments, 24 bytes each).
+// Larger batches loop over launches.
+constexpr int kMaxMx8SegsPerLaunch = 32;
+
+// The pairwise all-to-all head: the variable-count, optionally indexed
+// sibling of launch_mx8_quantize_blocks. `in` is [rows][S][after] contiguous
+// of `dtype`. Segment p is the stream of L_p = rows*count_p*after elements
+// in[b][slice(displ_p + c)][a] in (b, c, a) order, where slice(s) = idx[s]
+// with an index and s without one; it is quantized in groups of 32 that start
+// at the segment, G_p = ceil(L_p/32) groups to payload + 32*goff_p and
+// scales + goff_p, byte for byte what launch_mx8_quantize gives on a
+// contiguous copy of the segment (zero-padded partial last group included).
+// The caller guarantees displ_p + count_p <= S without an index and <= the
+// length of idx with one; an idx entry outside [0, S) reads as a slice of
+// zeros. A segment with count 0 writes nothing.
+void launch_mx8_quantize_segments(const void* in, const int64_t* idx,
+                                  void* payload, void* scales,
+                                  const Mx8SegDesc* segs, int nsegs,
+                                  int64_t rows, int64_t S, int64_t after,
+                                  int dtype, hipStream_t stream);
+// The pairwise all-to-all tail, the mirror of the above: segment p's stream
+// is dequantized into out[b][slice(displ_p + c)][a] of the contiguous
+// [rows][S][after] output of `dtype`. Writes exactly L_p elements per
+// segment; an idx entry outside [0, S) drops its slice.
+void launch_mx8_dequantize_segments(const void* payload, const void* scales,
+                                    const int64_t* idx, void* out,
+                                    const Mx8SegDesc* segs, int nsegs,
+                                    int64_t rows, int64_t S, int64_t after,
+                                    int dtype, hipStream_t stream);
+
 } // namespace m4a

@@ -14,7 +14,7 @@
 //     hardware RNE f32->e4m3 of hip_fp8.h, which cannot saturate because
 //     amax*2^-E <= 448 by construction.
 //
-// Six streaming kernels, all 256-thread workgroups, grid-stride, 16-byte
+// Eight streaming kernels, all 256-thread workgroups, grid-stride, 16-byte
 // accesses on the wide side, nontemporal (every byte is touched once):
 //   quantize   : 8 lanes x 16 B per fp32 group, 4 lanes x 16 B per 16-bit
 //                group; amax crosses the lanes with 3 / 2 xor-shuffles;
@@ -37,12 +37,18 @@
 //                kernel's lane layout over the P blocks of a
 //                [rows][P][row_elems] input read in place (grid.y = block),
 //                one mxfp8 stream per block out.
+//   quantize_segments / dequantize_segments : the pairwise all-to-all head
+//                and tail — the two _blocks layouts over segments of
+//                variable slice counts (grid.y = segment, descriptors by
+//                value), optionally gathering / scattering slices through
+//                an int64 index while they read / write.
 // The first four have a one-thread-per-group scalar twin for base pointers
 // that miss the vector alignment (e.g. a contiguous x[1:] view); the partial
 // last group of their vector kernels goes through the same scalar group
 // routine. dequantize_blocks has a general twin that still stores aligned
 // 16-byte chunks (see there); quantize_blocks has a one-thread-per-group twin
-// with element-wise index mapping.
+// with element-wise index mapping; the segments kernels have
+// one-thread-per-group twins on both sides.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp8.h>
@@ -799,6 +805,260 @@ __global__ __launch_bounds__(256) void mx8_quantize_blocks_kernel_scalar(
   }
 }
 
+// ---- segments (the pairwise all-to-all head and tail) --------------------
+//
+// The variable-count, optionally indexed siblings of the two kernels above.
+// The tensor side is [rows][S][after] contiguous; segment p covers stream
+// slices [displ_p, displ_p + count_p), its stream of L_p = rows*count_p*after
+// elements in (b, c, a) order has G_p = ceil(L_p/32) groups, payload at byte
+// 32*goff_p and scales at byte goff_p. Stream slice c of segment p is tensor
+// slice idx[displ_p + c] with an index, displ_p + c without one. grid.y is
+// the segment, so the descriptor (by value in the kernel arguments) is
+// wave-uniform; grid.x is sized for the largest segment of the launch and a
+// segment with count 0 returns at once.
+//
+// Vector bodies require after % EPL == 0 and aligned bases: every 16-byte
+// chunk lies inside one slice. MODE picks the chunk -> tensor mapping:
+//   0  no index: the rows of a segment are contiguous runs of count*after,
+//      one division by the run length in chunks (as in the _blocks kernels);
+//   1  index, rows == 1 (the MoE token case): one division by the slice
+//      length in chunks, then the index load;
+//   2  index, rows > 1: two divisions.
+// The index load is a plain cached 8-byte load: all chunks of a slice share
+// it. An index outside [0, S) gives -1: zeros on the quantize side, nothing
+// stored on the dequantize side.
+
+struct SegArgs {
+  Mx8SegDesc s[kMaxMx8SegsPerLaunch];
+};
+
+template <typename I, int MODE>
+__device__ inline long long seg_chunk(I i, long long displ,
+                                      const long long* __restrict__ idx,
+                                      long long S, I cps, I cpr) {
+  if constexpr (MODE == 0) {
+    const I row = i / cpr;
+    const I col = i - row * cpr;
+    return ((long long)row * S + displ) * (long long)cps + (long long)col;
+  } else if constexpr (MODE == 1) {
+    const I c = i / cps;
+    const I col = i - c * cps;
+    const long long t = idx[displ + (long long)c];
+    return (unsigned long long)t < (unsigned long long)S
+               ? t * (long long)cps + (long long)col
+               : -1;
+  } else {
+    const I row = i / cpr;
+    const I rem = i - row * cpr;
+    const I c = rem / cps;
+    const I col = rem - c * cps;
+    const long long t = idx[displ + (long long)c];
+    return (unsigned long long)t < (unsigned long long)S
+               ? ((long long)row * S + t) * (long long)cps + (long long)col
+               : -1;
+  }
+}
+
+// The quantize kernel's lane layout over ALL G_p*LPG lane slots of the
+// segment (wave-uniform trip count: the shuffles and the scale gather need
+// every lane). Slots past L_p/EPL count as zeros and store the zero padding,
+// so the partial last group needs no scalar tail. The scales base sc + goff
+// has any alignment: store_scales falls back to per-lane bytes.
+template <int K, typename I, int MODE>
+__global__ __launch_bounds__(256) void mx8_quantize_segments_kernel(
+    const void* __restrict__ in, const long long* __restrict__ idx,
+    u8* __restrict__ pay, u8* __restrict__ sc, SegArgs segs, long long S,
+    I cps, long long rows) {
+  constexpr int LPG = K == kF32 ? 8 : 4;
+  constexpr int EPL = 32 / LPG;
+  const long long count = segs.s[blockIdx.y].count;
+  if (count == 0) return;
+  const long long displ = segs.s[blockIdx.y].displ;
+  const long long goff = segs.s[blockIdx.y].goff;
+  const I cpr = (I)count * cps;
+  const I chunks = (I)rows * cpr;
+  const long long G = ((long long)chunks + LPG - 1) / LPG;
+  const I slots = (I)(G * LPG);
+  u8* __restrict__ bp = pay + goff * 32;
+  u8* __restrict__ bs = sc + goff;
+  const I stride = (I)gridDim.x * blockDim.x;
+  const int lane = threadIdx.x & 63;
+  for (I i0 = (I)blockIdx.x * blockDim.x + (threadIdx.x & ~63); i0 < slots;
+       i0 += stride) {
+    const I i = i0 + lane;
+    float x[EPL];
+    long long src = -1;
+    if (i < chunks) src = seg_chunk<I, MODE>(i, displ, idx, S, cps, cpr);
+    if (src >= 0) {
+      const v4u w =
+          __builtin_nontemporal_load(reinterpret_cast<const v4u*>(in) + src);
+      unpack16<K, EPL>(w, x);
+    } else {
+      for (int k = 0; k < EPL; ++k) x[k] = 0.0f;
+    }
+    unsigned a = amax_bits_of(x);
+    for (int m = 1; m < LPG; m <<= 1) {
+      const unsigned o = (unsigned)__shfl_xor((int)a, m);
+      a = o > a ? o : a;
+    }
+    int E;
+    const int sb = mx8_scale_byte(a, &E);
+    if (i < slots) {
+      if constexpr (K == kF32) {
+        const unsigned o = sb == 255 ? 0u : quant4(x[0], x[1], x[2], x[3], E);
+        __builtin_nontemporal_store(o, reinterpret_cast<unsigned*>(bp) + i);
+      } else {
+        v2u o;
+        o[0] = sb == 255 ? 0u : quant4(x[0], x[1], x[2], x[3], E);
+        o[1] = sb == 255
+                   ? 0u
+                   : quant4(x[EPL - 4], x[EPL - 3], x[EPL - 2], x[EPL - 1], E);
+        __builtin_nontemporal_store(o, reinterpret_cast<v2u*>(bp) + i);
+      }
+    }
+    store_scales<LPG>(bs, (long long)(i0 / LPG), G, sb, lane);
+  }
+}
+
+// The dequantize kernel's lane layout over all L_p/EPL chunks of the
+// segment: whole chunks only, so nothing past element L_p is written. The
+// padded payload keeps the last group's loads inside the segment.
+template <int K, typename I, int MODE>
+__global__ __launch_bounds__(256) void mx8_dequantize_segments_kernel(
+    const u8* __restrict__ pay, const u8* __restrict__ sc,
+    const long long* __restrict__ idx, void* __restrict__ out, SegArgs segs,
+    long long S, I cps, long long rows) {
+  constexpr int LPG = K == kF32 ? 8 : 4;
+  constexpr int EPL = 32 / LPG;
+  const long long count = segs.s[blockIdx.y].count;
+  if (count == 0) return;
+  const long long displ = segs.s[blockIdx.y].displ;
+  const long long goff = segs.s[blockIdx.y].goff;
+  const I cpr = (I)count * cps;
+  const I chunks = (I)rows * cpr;
+  const u8* __restrict__ bp = pay + goff * 32;
+  const u8* __restrict__ bs = sc + goff;
+  const I stride = (I)gridDim.x * blockDim.x;
+  for (I i = (I)blockIdx.x * blockDim.x + threadIdx.x; i < chunks;
+       i += stride) {
+    const long long dst = seg_chunk<I, MODE>(i, displ, idx, S, cps, cpr);
+    if (dst < 0) continue;
+    const int sb = bs[i / LPG];
+    unsigned w[EPL / 4];
+    if constexpr (K == kF32) {
+      w[0] = __builtin_nontemporal_load(
+          reinterpret_cast<const unsigned*>(bp) + i);
+    } else {
+      const v2u t =
+          __builtin_nontemporal_load(reinterpret_cast<const v2u*>(bp) + i);
+      w[0] = t[0];
+      w[EPL / 4 - 1] = t[1];
+    }
+    float x[EPL];
+    for (int d = 0; d < EPL / 4; ++d) {
+      for (int k = 0; k < 4; ++k) {
+        x[4 * d + k] = mx8_dequant((u8)(w[d] >> (8 * k)), sb);
+      }
+    }
+    __builtin_nontemporal_store(pack16<K, EPL>(x),
+                                reinterpret_cast<v4u*>(out) + dst);
+  }
+}
+
+// General twins: any slice length, any alignment of the bases (an odd
+// `after`, a contiguous x[1:] view). One thread per group on both sides, like
+// the first four kernels' twins: the group's first element is mapped to
+// (b, c, a) with two divisions and the 32 elements are walked from there,
+// the slice index reloaded whenever c changes. Token rows of an MoE layer
+// (after % EPL == 0, allocator-aligned bases) never take them.
+template <int K, bool IDX>
+__global__ __launch_bounds__(256) void mx8_quantize_segments_kernel_scalar(
+    const void* __restrict__ in, const long long* __restrict__ idx,
+    u8* __restrict__ pay, u8* __restrict__ sc, SegArgs segs, long long S,
+    long long after, long long rows) {
+  using T = typename Elem<K>::type;
+  const long long count = segs.s[blockIdx.y].count;
+  if (count == 0) return;
+  const long long displ = segs.s[blockIdx.y].displ;
+  const long long goff = segs.s[blockIdx.y].goff;
+  const long long run = count * after;
+  const long long L = rows * run;
+  const long long G = (L + 31) / 32;
+  const T* __restrict__ src = reinterpret_cast<const T*>(in);
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < G;
+       g += stride) {
+    const long long e0 = g * 32;
+    long long b = e0 / run;
+    const long long rem = e0 - b * run;
+    long long c = rem / after;
+    long long a = rem - c * after;
+    long long t = IDX ? idx[displ + c] : displ + c;
+    float x[32];
+    for (int k = 0; k < 32; ++k) {
+      if (e0 + k < L) {
+        const bool ok = (unsigned long long)t < (unsigned long long)S;
+        x[k] = ok ? elem_to_f32<K>(src[(b * S + t) * after + a]) : 0.0f;
+        if (++a == after) {
+          a = 0;
+          if (++c == count) {
+            c = 0;
+            ++b;
+          }
+          if (e0 + k + 1 < L) t = IDX ? idx[displ + c] : displ + c;
+        }
+      } else {
+        x[k] = 0.0f;
+      }
+    }
+    encode_group_scalar(x, pay + (goff + g) * 32, sc + goff + g);
+  }
+}
+
+template <int K, bool IDX>
+__global__ __launch_bounds__(256) void mx8_dequantize_segments_kernel_scalar(
+    const u8* __restrict__ pay, const u8* __restrict__ sc,
+    const long long* __restrict__ idx, void* __restrict__ out, SegArgs segs,
+    long long S, long long after, long long rows) {
+  using T = typename Elem<K>::type;
+  const long long count = segs.s[blockIdx.y].count;
+  if (count == 0) return;
+  const long long displ = segs.s[blockIdx.y].displ;
+  const long long goff = segs.s[blockIdx.y].goff;
+  const long long run = count * after;
+  const long long L = rows * run;
+  const long long G = (L + 31) / 32;
+  T* __restrict__ dst = reinterpret_cast<T*>(out);
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < G;
+       g += stride) {
+    const long long e0 = g * 32;
+    long long b = e0 / run;
+    const long long rem = e0 - b * run;
+    long long c = rem / after;
+    long long a = rem - c * after;
+    long long t = IDX ? idx[displ + c] : displ + c;
+    const int sb = sc[goff + g];
+    const u8* __restrict__ p = pay + (goff + g) * 32;
+    for (int k = 0; k < 32; ++k) {
+      if (e0 + k < L) {
+        if ((unsigned long long)t < (unsigned long long)S) {
+          dst[(b * S + t) * after + a] =
+              f32_to_elem<K>(mx8_dequant(p[k], sb));
+        }
+        if (++a == after) {
+          a = 0;
+          if (++c == count) {
+            c = 0;
+            ++b;
+          }
+          if (e0 + k + 1 < L) t = IDX ? idx[displ + c] : displ + c;
+        }
+      }
+    }
+  }
+}
+
 inline unsigned grid_for(long long work) {
   long long blocks = (work + 255) / 256;
   if (blocks > 4096) blocks = 4096;
@@ -966,7 +1226,232 @@ void launch_quantize_blocks_t(const void* in, u8* pay, u8* sc, int nblocks,
   }
 }
 
+// One launch's worth of segments: the descriptors by value, the largest
+// count (grid.x is sized for it) and the number of non-empty segments.
+struct SegBatch {
+  SegArgs args{};
+  int n = 0;
+  long long max_count = 0;
+};
+
+inline SegBatch seg_batch(const Mx8SegDesc* segs, int n) {
+  SegBatch b;
+  b.n = n;
+  for (int k = 0; k < n; ++k) {
+    b.args.s[k] = segs[k];
+    if (segs[k].count > b.max_count) b.max_count = segs[k].count;
+  }
+  return b;
+}
+
+// grid.y carries the segment; grid.x is capped so the launch stays near the
+// 4096 workgroups of the siblings
+inline dim3 seg_grid(long long work, int nsegs) {
+  const long long xcap = 4096 / nsegs > 0 ? 4096 / nsegs : 1;
+  long long x = (work + 255) / 256;
+  if (x > xcap) x = xcap;
+  if (x < 1) x = 1;
+  return dim3((unsigned)x, (unsigned)nsegs);
+}
+
+// With no index, rows == 1 and every L_p a multiple of 32, segments that
+// follow each other on both sides form one flat mxfp8 stream. Returns its
+// element count, or -1 when the segments are not of that shape; *first
+// receives the first non-empty segment.
+inline long long flat_stream_of(const Mx8SegDesc* segs, int nsegs,
+                                int64_t after, int* first) {
+  long long total = 0;
+  *first = -1;
+  for (int k = 0; k < nsegs; ++k) {
+    if (segs[k].count == 0) continue;
+    const long long L = segs[k].count * after;
+    if (L % 32 != 0) return -1;
+    if (*first < 0) {
+      *first = k;
+    } else {
+      const Mx8SegDesc& f = segs[*first];
+      if ((segs[k].displ - f.displ) * after != total ||
+          (segs[k].goff - f.goff) * 32 != total) {
+        return -1;
+      }
+    }
+    total += L;
+  }
+  return total;
+}
+
+template <int K, typename I, int MODE>
+void launch_qseg(const void* in, const long long* idx, u8* pay, u8* sc,
+                 const SegBatch& b, long long slots, int64_t rows, int64_t S,
+                 long long cps, hipStream_t stream) {
+  hipLaunchKernelGGL((mx8_quantize_segments_kernel<K, I, MODE>),
+                     seg_grid(slots, b.n), dim3(256), 0, stream, in, idx, pay,
+                     sc, b.args, (long long)S, (I)cps, (long long)rows);
+}
+
+template <int K, typename I, int MODE>
+void launch_dseg(const u8* pay, const u8* sc, const long long* idx, void* out,
+                 const SegBatch& b, long long chunks, int64_t rows, int64_t S,
+                 long long cps, hipStream_t stream) {
+  hipLaunchKernelGGL((mx8_dequantize_segments_kernel<K, I, MODE>),
+                     seg_grid(chunks, b.n), dim3(256), 0, stream, pay, sc, idx,
+                     out, b.args, (long long)S, (I)cps, (long long)rows);
+}
+
+template <int K>
+void launch_quantize_segments_t(const void* in, const long long* idx, u8* pay,
+                                u8* sc, const Mx8SegDesc* segs, int nsegs,
+                                int64_t rows, int64_t S, int64_t after,
+                                hipStream_t stream) {
+  using T = typename Elem<K>::type;
+  constexpr int LPG = K == kF32 ? 8 : 4;
+  constexpr int EPL = 32 / LPG;
+  // Every segment's payload base is pay + 32*goff, so an aligned pay keeps
+  // all of them aligned; after % EPL == 0 with an aligned in keeps every
+  // chunk's source aligned.
+  const bool al = aligned(in, 16) && aligned(pay, 32 / LPG);
+  if (al && idx == nullptr && rows == 1) {
+    int first;
+    const long long total = flat_stream_of(segs, nsegs, after, &first);
+    if (total == 0) return;
+    if (total > 0) {
+      const T* base = reinterpret_cast<const T*>(in) + segs[first].displ * after;
+      if (aligned(base, 16)) {
+        launch_quantize_t<K>(base, pay + segs[first].goff * 32,
+                             sc + segs[first].goff, total, stream);
+        return;
+      }
+    }
+  }
+  for (int s0 = 0; s0 < nsegs; s0 += kMaxMx8SegsPerLaunch) {
+    const int n = nsegs - s0 < kMaxMx8SegsPerLaunch ? nsegs - s0
+                                                    : kMaxMx8SegsPerLaunch;
+    const SegBatch b = seg_batch(segs + s0, n);
+    if (b.max_count == 0) continue;
+    if (al && after % EPL == 0) {
+      const long long cps = after / EPL;
+      const long long chunks = rows * b.max_count * cps;
+      const long long slots = (chunks + LPG - 1) / LPG * LPG;
+      const bool small = slots < (1ll << 31);
+      if (idx == nullptr) {
+        if (small) launch_qseg<K, unsigned, 0>(in, idx, pay, sc, b, slots, rows, S, cps, stream);
+        else launch_qseg<K, long long, 0>(in, idx, pay, sc, b, slots, rows, S, cps, stream);
+      } else if (rows == 1) {
+        if (small) launch_qseg<K, unsigned, 1>(in, idx, pay, sc, b, slots, rows, S, cps, stream);
+        else launch_qseg<K, long long, 1>(in, idx, pay, sc, b, slots, rows, S, cps, stream);
+      } else {
+        if (small) launch_qseg<K, unsigned, 2>(in, idx, pay, sc, b, slots, rows, S, cps, stream);
+        else launch_qseg<K, long long, 2>(in, idx, pay, sc, b, slots, rows, S, cps, stream);
+      }
+    } else {
+      const long long G = (rows * b.max_count * after + 31) / 32;
+      if (idx == nullptr) {
+        hipLaunchKernelGGL((mx8_quantize_segments_kernel_scalar<K, false>),
+                           seg_grid(G, n), dim3(256), 0, stream, in, idx, pay,
+                           sc, b.args, (long long)S, (long long)after,
+                           (long long)rows);
+      } else {
+        hipLaunchKernelGGL((mx8_quantize_segments_kernel_scalar<K, true>),
+                           seg_grid(G, n), dim3(256), 0, stream, in, idx, pay,
+                           sc, b.args, (long long)S, (long long)after,
+                           (long long)rows);
+      }
+    }
+  }
+}
+
+template <int K>
+void launch_dequantize_segments_t(const u8* pay, const u8* sc,
+                                  const long long* idx, void* out,
+                                  const Mx8SegDesc* segs, int nsegs,
+                                  int64_t rows, int64_t S, int64_t after,
+                                  hipStream_t stream) {
+  using T = typename Elem<K>::type;
+  constexpr int LPG = K == kF32 ? 8 : 4;
+  constexpr int EPL = 32 / LPG;
+  const bool al = aligned(out, 16) && aligned(pay, 32 / LPG);
+  if (al && idx == nullptr && rows == 1) {
+    int first;
+    const long long total = flat_stream_of(segs, nsegs, after, &first);
+    if (total == 0) return;
+    if (total > 0) {
+      T* base = reinterpret_cast<T*>(out) + segs[first].displ * after;
+      if (aligned(base, 16)) {
+        launch_dequantize_t<K>(pay + segs[first].goff * 32,
+                               sc + segs[first].goff, base, total, stream);
+        return;
+      }
+    }
+  }
+  for (int s0 = 0; s0 < nsegs; s0 += kMaxMx8SegsPerLaunch) {
+    const int n = nsegs - s0 < kMaxMx8SegsPerLaunch ? nsegs - s0
+                                                    : kMaxMx8SegsPerLaunch;
+    const SegBatch b = seg_batch(segs + s0, n);
+    if (b.max_count == 0) continue;
+    if (al && after % EPL == 0) {
+      const long long cps = after / EPL;
+      const long long chunks = rows * b.max_count * cps;
+      const bool small = chunks < (1ll << 31);
+      if (idx == nullptr) {
+        if (small) launch_dseg<K, unsigned, 0>(pay, sc, idx, out, b, chunks, rows, S, cps, stream);
+        else launch_dseg<K, long long, 0>(pay, sc, idx, out, b, chunks, rows, S, cps, stream);
+      } else if (rows == 1) {
+        if (small) launch_dseg<K, unsigned, 1>(pay, sc, idx, out, b, chunks, rows, S, cps, stream);
+        else launch_dseg<K, long long, 1>(pay, sc, idx, out, b, chunks, rows, S, cps, stream);
+      } else {
+        if (small) launch_dseg<K, unsigned, 2>(pay, sc, idx, out, b, chunks, rows, S, cps, stream);
+        else launch_dseg<K, long long, 2>(pay, sc, idx, out, b, chunks, rows, S, cps, stream);
+      }
+    } else {
+      const long long G = (rows * b.max_count * after + 31) / 32;
+      if (idx == nullptr) {
+        hipLaunchKernelGGL((mx8_dequantize_segments_kernel_scalar<K, false>),
+                           seg_grid(G, n), dim3(256), 0, stream, pay, sc, idx,
+                           out, b.args, (long long)S, (long long)after,
+                           (long long)rows);
+      } else {
+        hipLaunchKernelGGL((mx8_dequantize_segments_kernel_scalar<K, true>),
+                           seg_grid(G, n), dim3(256), 0, stream, pay, sc, idx,
+                           out, b.args, (long long)S, (long long)after,
+                           (long long)rows);
+      }
+    }
+  }
+}
+
 } // namespace
+
+void launch_mx8_quantize_segments(const void* in, const int64_t* idx,
+                                  void* payload, void* scales,
+                                  const Mx8SegDesc* segs, int nsegs,
+                                  int64_t rows, int64_t S, int64_t after,
+                                  int dtype, hipStream_t stream) {
+  if (nsegs <= 0 || rows <= 0 || S <= 0 || after <= 0) return;
+  const long long* ix = reinterpret_cast<const long long*>(idx);
+  u8* pay = static_cast<u8*>(payload);
+  u8* sc = static_cast<u8*>(scales);
+  switch (dtype) {
+    case 0: launch_quantize_segments_t<kF32>(in, ix, pay, sc, segs, nsegs, rows, S, after, stream); break;
+    case 1: launch_quantize_segments_t<kBF16>(in, ix, pay, sc, segs, nsegs, rows, S, after, stream); break;
+    default: launch_quantize_segments_t<kF16>(in, ix, pay, sc, segs, nsegs, rows, S, after, stream); break;
+  }
+}
+
+void launch_mx8_dequantize_segments(const void* payload, const void* scales,
+                                    const int64_t* idx, void* out,
+                                    const Mx8SegDesc* segs, int nsegs,
+                                    int64_t rows, int64_t S, int64_t after,
+                                    int dtype, hipStream_t stream) {
+  if (nsegs <= 0 || rows <= 0 || S <= 0 || after <= 0) return;
+  const long long* ix = reinterpret_cast<const long long*>(idx);
+  const u8* pay = static_cast<const u8*>(payload);
+  const u8* sc = static_cast<const u8*>(scales);
+  switch (dtype) {
+    case 0: launch_dequantize_segments_t<kF32>(pay, sc, ix, out, segs, nsegs, rows, S, after, stream); break;
+    case 1: launch_dequantize_segments_t<kBF16>(pay, sc, ix, out, segs, nsegs, rows, S, after, stream); break;
+    default: launch_dequantize_segments_t<kF16>(pay, sc, ix, out, segs, nsegs, rows, S, after, stream); break;
+  }
+}
 
 void launch_mx8_quantize_blocks(const void* in, void* payload, void* scales,
                                 int nblocks, int64_t rows, int64_t row_elems,

@@ -1147,6 +1147,169 @@ Tensor mx8_alltoall(Transport& tr, const Tensor& in, int64_t rows_s,
                                in.scalar_type());
 }
 
+// Segment layout of the variable-count codec: segment p covers `counts[p]`
+// stream slices from the prefix sum on, L_p = rows*counts[p]*after elements,
+// G_p = ceil(L_p/32) groups from group goff_p = sum_{q<p} G_q on.
+struct Mx8SegPlan {
+  std::vector<Mx8SegDesc> segs;
+  std::vector<int64_t> groups;  // G_p
+  int64_t slices = 0;           // sum of counts
+  int64_t total_groups = 0;     // sum of G_p
+};
+
+Mx8SegPlan mx8_seg_plan(const std::vector<int64_t>& counts, int64_t rows,
+                        int64_t after) {
+  Mx8SegPlan pl;
+  pl.segs.reserve(counts.size());
+  pl.groups.reserve(counts.size());
+  for (int64_t c : counts) {
+    TORCH_CHECK(c >= 0, "mpi4torch_amd: negative segment count ", c);
+    const int64_t G = (rows * c * after + 31) / 32;
+    pl.segs.push_back(Mx8SegDesc{pl.slices, c, pl.total_groups});
+    pl.groups.push_back(G);
+    pl.slices += c;
+    pl.total_groups += G;
+  }
+  return pl;
+}
+
+// `in`: contiguous, seen as [rows, S, after]. The pairwise all-to-all head,
+// normative here: with xs = in.index_select(1, order) if `order` is given,
+// else in, segment p is mx8_quantize of the contiguous copy of
+// xs[:, displ_p : displ_p + counts[p], :] — groups start at the segment, the
+// partial last group is zero-padded. Returns (payload [32*sum G_p], scales
+// [sum G_p]) with the segments' streams one after the other. sum(counts)
+// must equal S without an order and the order's length with one.
+std::pair<Tensor, Tensor> mx8_quantize_segments(
+    const Tensor& in, int64_t rows, int64_t after,
+    const std::vector<int64_t>& counts, const c10::optional<Tensor>& order,
+    const c10::optional<Tensor>& payload_out = c10::nullopt,
+    const c10::optional<Tensor>& scales_out = c10::nullopt) {
+  const int dt = mx8_dtype_code(in.scalar_type());
+  const auto pl = mx8_seg_plan(counts, rows, after);
+  const int64_t S = rows * after > 0 ? in.numel() / (rows * after) : 0;
+  auto bopts = in.options().dtype(at::kByte);
+  auto pay = payload_out.has_value()
+                 ? payload_out->narrow(0, 0, pl.total_groups * 32)
+                 : at::empty({pl.total_groups * 32}, bopts);
+  auto sc = scales_out.has_value() ? scales_out->narrow(0, 0, pl.total_groups)
+                                   : at::empty({pl.total_groups}, bopts);
+  if (pl.total_groups == 0) return {pay, sc};
+  if (in.is_cuda()) {
+    launch_mx8_quantize_segments(
+        in.data_ptr(),
+        order.has_value() ? order->data_ptr<int64_t>() : nullptr,
+        pay.data_ptr(), sc.data_ptr(), pl.segs.data(), (int)pl.segs.size(),
+        rows, S, after, dt, current_gpu_stream(in));
+    return {pay, sc};
+  }
+  auto xs = in.view({rows, S, after});
+  if (order.has_value()) xs = xs.index_select(1, *order);
+  for (size_t p = 0; p < counts.size(); ++p) {
+    if (pl.groups[p] == 0) continue;
+    auto q = mx8_quantize(
+        xs.narrow(1, pl.segs[p].displ, counts[p]).contiguous().view({-1}));
+    pay.narrow(0, pl.segs[p].goff * 32, pl.groups[p] * 32).copy_(q.first);
+    sc.narrow(0, pl.segs[p].goff, pl.groups[p]).copy_(q.second);
+  }
+  return {pay, sc};
+}
+
+// The pairwise all-to-all tail, normative here: segment p's stream (layout
+// as above, R = sum(counts)) gives
+//   y[:, displ_p : displ_p + counts[p], :] = dq(segment p)[:L_p].to(dtype)
+// and the result [rows, R, after] is y without an order, else a tensor with
+// out.index_copy_(1, order, y): received slice i lands at slice order[i].
+// `out` (contiguous [rows, R, after]) is written in place when given; slices
+// no order entry names keep their contents.
+Tensor mx8_dequantize_segments(const Tensor& pay, const Tensor& sc,
+                               int64_t rows, int64_t after,
+                               const std::vector<int64_t>& counts,
+                               const c10::optional<Tensor>& order,
+                               at::ScalarType dtype,
+                               const c10::optional<Tensor>& out_opt =
+                                   c10::nullopt) {
+  const int dt = mx8_dtype_code(dtype);
+  const auto pl = mx8_seg_plan(counts, rows, after);
+  auto out = out_opt.has_value()
+                 ? *out_opt
+                 : at::empty({rows, pl.slices, after},
+                             pay.options().dtype(dtype));
+  if (pl.total_groups == 0) return out;
+  if (pay.is_cuda()) {
+    launch_mx8_dequantize_segments(
+        pay.data_ptr(), sc.data_ptr(),
+        order.has_value() ? order->data_ptr<int64_t>() : nullptr,
+        out.data_ptr(), pl.segs.data(), (int)pl.segs.size(), rows, pl.slices,
+        after, dt, current_gpu_stream(pay));
+    return out;
+  }
+  auto y = order.has_value() ? at::empty({rows, pl.slices, after},
+                                         pay.options().dtype(dtype))
+                             : out;
+  for (size_t p = 0; p < counts.size(); ++p) {
+    if (pl.groups[p] == 0) continue;
+    const int64_t G = pl.groups[p];
+    auto d = mx8_dequantize_groups(
+                 pay.narrow(0, pl.segs[p].goff * 32, G * 32).view({G, 32}),
+                 sc.narrow(0, pl.segs[p].goff, G))
+                 .view({-1});
+    y.narrow(1, pl.segs[p].displ, counts[p])
+        .copy_(d.narrow(0, 0, rows * counts[p] * after)
+                   .to(dtype)
+                   .view({rows, counts[p], after}));
+  }
+  if (order.has_value()) out.index_copy_(1, *order, y);
+  return out;
+}
+
+// The pairwise all-to-all of the family: `in` is this rank's contiguous
+// tensor seen as [rows, S, after]. The fused head gathers slices through
+// send_order while it quantizes segment p (what rank p receives) in groups of
+// 32 that start at the segment; payload and scales travel as two contiguous
+// pieces per peer in ONE grouped call, their sizes 32*G and G computed from
+// the counts both ends know; the fused tail dequantizes the received
+// segments, the own one included, straight into [rows, R, after], scattering
+// slices through recv_order while it writes. No index_select pass on either
+// side; every value is quantized exactly once. Both transports skip
+// zero-length pieces on both ends of a pair, and so does this: an empty
+// segment is not listed at all.
+Tensor mx8_alltoall_pairwise(Transport& tr, const Tensor& in, int64_t rows,
+                             int64_t after,
+                             const std::vector<int64_t>& send_counts,
+                             const std::vector<int64_t>& recv_counts,
+                             const c10::optional<Tensor>& send_order,
+                             const c10::optional<Tensor>& recv_order) {
+  const int P = tr.size();
+  const auto sp = mx8_seg_plan(send_counts, rows, after);
+  const auto rp = mx8_seg_plan(recv_counts, rows, after);
+  auto q = mx8_quantize_segments(in, rows, after, send_counts, send_order);
+  auto bopts = in.options().dtype(at::kByte);
+  auto stg_pay = at::empty({rp.total_groups * 32}, bopts);
+  auto stg_sc = at::empty({rp.total_groups}, bopts);
+  std::vector<Tensor> sends, recvs;
+  std::vector<int> speers, rpeers;
+  for (int p = 0; p < P; ++p) {
+    if (sp.groups[p] > 0) {
+      sends.push_back(
+          q.first.narrow(0, sp.segs[p].goff * 32, sp.groups[p] * 32));
+      sends.push_back(q.second.narrow(0, sp.segs[p].goff, sp.groups[p]));
+      speers.push_back(p);
+      speers.push_back(p);
+    }
+    if (rp.groups[p] > 0) {
+      recvs.push_back(
+          stg_pay.narrow(0, rp.segs[p].goff * 32, rp.groups[p] * 32));
+      recvs.push_back(stg_sc.narrow(0, rp.segs[p].goff, rp.groups[p]));
+      rpeers.push_back(p);
+      rpeers.push_back(p);
+    }
+  }
+  tr.exchange(sends, speers, recvs, rpeers);
+  return mx8_dequantize_segments(stg_pay, stg_sc, rows, after, recv_counts,
+                                 recv_order, in.scalar_type());
+}
+
 // The mxfp8 sibling of hierarchical_allreduce: quantize once, exchange each
 // rank's copy of group-block j to rank j (payload and scales as two
 // contiguous pieces per peer in ONE grouped call), fused
@@ -2708,6 +2871,157 @@ Tensor Communicator::AlltoallPairwise(const Tensor& input, int64_t axis,
 }
 
 // ---------------------------------------------------------------------------
+// AlltoallPairwiseCompressed (MI355X extension; not in the reference API):
+// AlltoallPairwise over the mxfp8 wire with the token permute fused into the
+// codec kernels — the expert-parallel dispatch/combine primitive.
+// ---------------------------------------------------------------------------
+
+namespace {
+struct AlltoallPairwiseCompressedBackward : public M4ANode {
+  AlltoallPairwiseCompressedBackward(int64_t axis, std::vector<int64_t> send,
+                                     std::vector<int64_t> recv,
+                                     c10::optional<Tensor> send_order,
+                                     c10::optional<Tensor> recv_order)
+      : axis(axis), send(std::move(send)), recv(std::move(recv)),
+        send_order(std::move(send_order)),
+        recv_order(std::move(recv_order)) {}
+  std::string name() const override {
+    return "M4AAlltoallPairwiseCompressedBackward";
+  }
+  variable_list apply(variable_list&& grads) override {
+    variable_list out(1);
+    if (should_compute_output(0)) {
+      // exact adjoint of gather -> exchange -> scatter for permutations:
+      // counts and orders swap; quantization is straight-through, and the
+      // gradient itself travels compressed
+      out[0] = comm->AlltoallPairwiseCompressed(grads[0], axis, recv, send,
+                                                recv_order, send_order);
+    }
+    return out;
+  }
+  int64_t axis;
+  std::vector<int64_t> send, recv;
+  c10::optional<Tensor> send_order, recv_order;
+};
+
+// Shape, dtype and device always; the permutation property on the CPU, and
+// on the GPU only under the desync detector's debug mode (it costs a sync).
+void check_pairwise_order(const char* which,
+                          const c10::optional<Tensor>& order, int64_t len,
+                          const Tensor& input) {
+  if (!order.has_value()) return;
+  const Tensor& o = *order;
+  TORCH_CHECK(o.dim() == 1 && o.numel() == len,
+              "AlltoallPairwiseCompressed: ", which, " must be a 1-D tensor "
+              "of length ", len, " (the sum of its counts), got shape ",
+              o.sizes());
+  TORCH_CHECK(o.scalar_type() == at::kLong,
+              "AlltoallPairwiseCompressed: ", which, " must be an int64 "
+              "tensor, got ", o.scalar_type());
+  TORCH_CHECK(o.device() == input.device(),
+              "AlltoallPairwiseCompressed: ", which, " must be on the "
+              "tensor's device ", input.device(), ", got ", o.device());
+  if (len > 0 && (!o.is_cuda() || config().debug_collectives)) {
+    const bool perm = std::get<0>(o.sort()).equal(
+        at::arange(len, o.options()));
+    TORCH_CHECK(perm, "AlltoallPairwiseCompressed: ", which, " must be a "
+                "permutation of 0..", len - 1);
+  }
+}
+} // namespace
+
+Tensor Communicator::AlltoallPairwiseCompressed(
+    const Tensor& input, int64_t axis, std::vector<int64_t> send_counts,
+    std::vector<int64_t> recv_counts, c10::optional<Tensor> send_order,
+    c10::optional<Tensor> recv_order) {
+  TORCH_CHECK(input.scalar_type() == at::kFloat ||
+                  input.scalar_type() == at::kBFloat16 ||
+                  input.scalar_type() == at::kHalf,
+              "mpi4torch_amd: AlltoallPairwiseCompressed supports float32, "
+              "bfloat16 and float16 tensors, got ", input.scalar_type());
+  axis = at::maybe_wrap_dim(axis, input.dim());
+  auto& tr0 = cpu_tr();
+  const int P = tr0.size();
+  TORCH_CHECK((int)send_counts.size() == P,
+              "AlltoallPairwiseCompressed: send_counts must have world_size "
+              "entries");
+  if (recv_counts.empty() && P > 1) {
+    // exchange the count matrix; my recv from j = j's send to me
+    auto mat = host_allgather_int64_vec(group_name_, send_counts);
+    recv_counts.resize(P);
+    const int me = tr0.rank();
+    for (int j = 0; j < P; ++j) recv_counts[j] = mat[(int64_t)j * P + me];
+  }
+  if (P == 1 && recv_counts.empty()) recv_counts = send_counts;
+  TORCH_CHECK((int)recv_counts.size() == P,
+              "AlltoallPairwiseCompressed: recv_counts must have world_size "
+              "entries");
+  int64_t s_total = 0, r_total = 0;
+  for (int64_t c : send_counts) {
+    TORCH_CHECK(c >= 0, "AlltoallPairwiseCompressed: negative send count ", c);
+    s_total += c;
+  }
+  for (int64_t c : recv_counts) {
+    TORCH_CHECK(c >= 0, "AlltoallPairwiseCompressed: negative recv count ", c);
+    r_total += c;
+  }
+  TORCH_CHECK(input.size(axis) == s_total,
+              "AlltoallPairwiseCompressed: sum of send_counts (", s_total,
+              ") must equal the axis size (", input.size(axis), ")");
+  check_pairwise_order("send_order", send_order, s_total, input);
+  check_pairwise_order("recv_order", recv_order, r_total, input);
+
+  std::shared_ptr<M4ANode> grad_fn;
+  if (torch::autograd::compute_requires_grad(input)) {
+    grad_fn = make_node<AlltoallPairwiseCompressedBackward>(
+        c10::intrusive_ptr<Communicator>::unsafe_reclaim_from_nonowning(this),
+        axis, send_counts, recv_counts, send_order, recv_order);
+    grad_fn->set_next_edges(torch::autograd::collect_next_edges(input));
+  }
+  auto result = [&]() {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    DeviceStager stager(input);
+    auto in = stager.to_comm(input).contiguous().variable_data();
+    // the order tensors follow the input through the stager
+    c10::optional<Tensor> so, ro;
+    if (send_order.has_value()) {
+      so = stager.to_comm(*send_order).contiguous().variable_data();
+    }
+    if (recv_order.has_value()) {
+      ro = stager.to_comm(*recv_order).contiguous().variable_data();
+    }
+    auto& tr = tr_for(in);
+    auto outsizes = in.sizes().vec();
+    outsizes[axis] = r_total;
+    // World of one: nothing crosses a wire, so nothing is compressed — the
+    // result is the exact permutation. force_full_path runs the whole
+    // pipeline instead: mx8_quantize_segments, self-exchange,
+    // mx8_dequantize_segments.
+    if (tr.size() == 1 && !config().force_full_path) {
+      auto y = so.has_value() ? in.index_select(axis, *so) : fast_clone(in);
+      if (ro.has_value()) {
+        auto out = at::empty(outsizes, in.options());
+        out.index_copy_(axis, *ro, y);
+        y = out;
+      }
+      return stager.from_comm(std::move(y));
+    }
+    debug_check_axis_collective(group_name_, "AlltoallPairwiseCompressed",
+                                in, {axis}, {axis});
+    const auto g = axis_geom(in, axis);
+    if (g.before * g.after == 0) {
+      return stager.from_comm(at::empty(outsizes, in.options()));
+    }
+    return stager.from_comm(
+        mx8_alltoall_pairwise(tr, in, g.before, g.after, send_counts,
+                              recv_counts, so, ro)
+            .view(outsizes));
+  }();
+  attach_history(result, grad_fn);
+  return result;
+}
+
+// ---------------------------------------------------------------------------
 // Isend / Irecv / Wait (reference csrc/extension.cpp:1048-1265). The handle
 // is the same 3-tensor contract [meta, buffer, input]; the MPI_Request
 // becomes an entry in the request table (hipEvent on the p2p stream / c10d
@@ -3332,6 +3646,95 @@ std::tuple<Tensor, Tensor> debug_mx8_quantize_blocks(
     sh.copy_(ps.second);
   }
   return std::make_tuple(ph, sh);
+}
+
+std::tuple<Tensor, Tensor> debug_mx8_quantize_segments(
+    const Tensor& x, int64_t rows, int64_t after,
+    std::vector<int64_t> counts, const c10::optional<Tensor>& order,
+    const c10::optional<Tensor>& payload_out,
+    const c10::optional<Tensor>& scales_out) {
+  TORCH_CHECK(x.dim() == 1 && x.is_contiguous() && rows >= 1 && after >= 1 &&
+                  x.numel() % (rows * after) == 0,
+              "debug_mx8_quantize_segments expects a flat contiguous tensor "
+              "of rows*S*after elements");
+  TORCH_CHECK(payload_out.has_value() == scales_out.has_value(),
+              "debug_mx8_quantize_segments: payload_out and scales_out go "
+              "together");
+  const auto pl = mx8_seg_plan(counts, rows, after);
+  const int64_t S = x.numel() / (rows * after);
+  if (order.has_value()) {
+    TORCH_CHECK(order->dim() == 1 && order->numel() == pl.slices &&
+                    order->scalar_type() == at::kLong &&
+                    order->is_contiguous() && order->device() == x.device(),
+                "debug_mx8_quantize_segments: order must be a contiguous "
+                "int64 tensor of sum(counts) entries on x's device");
+  } else {
+    TORCH_CHECK(pl.slices == S, "debug_mx8_quantize_segments: sum(counts) "
+                "must equal the number of slices ", S);
+  }
+  if (payload_out.has_value()) {
+    // write the heads of caller buffers (canary tests)
+    const Tensor& po = *payload_out;
+    const Tensor& so = *scales_out;
+    TORCH_CHECK(po.dim() == 1 && po.is_contiguous() &&
+                    po.scalar_type() == at::kByte &&
+                    po.numel() >= pl.total_groups * 32 &&
+                    po.device() == x.device() && so.dim() == 1 &&
+                    so.is_contiguous() && so.scalar_type() == at::kByte &&
+                    so.numel() >= pl.total_groups &&
+                    so.device() == x.device(),
+                "debug_mx8_quantize_segments: payload_out and scales_out "
+                "must be flat contiguous uint8 tensors with at least "
+                "32*sum(G) and sum(G) elements");
+  }
+  auto ps = mx8_quantize_segments(x, rows, after, counts, order, payload_out,
+                                  scales_out);
+  return std::make_tuple(ps.first, ps.second);
+}
+
+Tensor debug_mx8_dequantize_segments(const Tensor& payload,
+                                     const Tensor& scales, int64_t rows,
+                                     int64_t after,
+                                     std::vector<int64_t> counts,
+                                     at::ScalarType dtype,
+                                     const c10::optional<Tensor>& order,
+                                     const c10::optional<Tensor>& out) {
+  TORCH_CHECK(rows >= 1 && after >= 1,
+              "debug_mx8_dequantize_segments: rows and after must be >= 1");
+  const auto pl = mx8_seg_plan(counts, rows, after);
+  TORCH_CHECK(payload.dim() == 1 && scales.dim() == 1 &&
+                  payload.is_contiguous() && scales.is_contiguous() &&
+                  payload.scalar_type() == at::kByte &&
+                  scales.scalar_type() == at::kByte &&
+                  payload.numel() == pl.total_groups * 32 &&
+                  scales.numel() == pl.total_groups &&
+                  payload.device() == scales.device(),
+              "debug_mx8_dequantize_segments expects flat contiguous uint8 "
+              "payload [32*sum(G)] and scales [sum(G)]");
+  if (order.has_value()) {
+    TORCH_CHECK(order->dim() == 1 && order->numel() == pl.slices &&
+                    order->scalar_type() == at::kLong &&
+                    order->is_contiguous() &&
+                    order->device() == payload.device(),
+                "debug_mx8_dequantize_segments: order must be a contiguous "
+                "int64 tensor of sum(counts) entries on the payload's "
+                "device");
+  }
+  if (!out.has_value()) {
+    return mx8_dequantize_segments(payload, scales, rows, after, counts, order,
+                                   dtype);
+  }
+  // write the first rows*R*after elements of a caller buffer (canary tests)
+  const int64_t total = rows * pl.slices * after;
+  const Tensor& o = *out;
+  TORCH_CHECK(o.dim() == 1 && o.is_contiguous() && o.numel() >= total &&
+                  o.scalar_type() == dtype && o.device() == payload.device(),
+              "debug_mx8_dequantize_segments: out must be a flat contiguous "
+              "tensor of the requested dtype with at least rows*R*after "
+              "elements");
+  auto head = o.narrow(0, 0, total).view({rows, pl.slices, after});
+  return mx8_dequantize_segments(payload, scales, rows, after, counts, order,
+                                 dtype, head);
 }
 
 Tensor debug_pairloc_reduce(const Tensor& stacked, int64_t op) {

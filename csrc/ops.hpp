@@ -104,6 +104,24 @@ struct Communicator : torch::CustomClassHolder {
                               std::vector<int64_t> send_counts,
                               std::vector<int64_t> recv_counts);
 
+  // AlltoallPairwise over the mxfp8 wire with the slice permute fused into
+  // the codec kernels (MI355X extension): the expert-parallel
+  // dispatch/combine primitive. With xs = input.index_select(axis,
+  // send_order) (or input), block j = xs[.., sdispl_j : +send_counts[j], ..]
+  // is quantized once in groups of 32 that start at the block and travels to
+  // rank j in one grouped exchange; the received blocks, the own one
+  // included, are dequantized into y along `axis` in rank order, and the
+  // result is y or, with recv_order, the tensor with
+  // out.index_copy_(axis, recv_order, y). Neither permute is a pass of its
+  // own: the gfx950 head gathers while it reads, the tail scatters while it
+  // writes. float32/bfloat16/float16 only; the orders are int64 permutations
+  // on the tensor's device. Backward: the same op on the gradient with
+  // counts and orders swapped. A world of one returns the exact permutation.
+  at::Tensor AlltoallPairwiseCompressed(
+      const at::Tensor& input, int64_t axis, std::vector<int64_t> send_counts,
+      std::vector<int64_t> recv_counts, c10::optional<at::Tensor> send_order,
+      c10::optional<at::Tensor> recv_order);
+
   // Non-blocking allreduce (MI355X-first overlap primitive, not in the
   // reference API): returns a wait handle; no autograd through it — use
   // Allreduce for differentiable paths. Gradient bucketing (parallel/ddp)
@@ -200,6 +218,25 @@ std::tuple<at::Tensor, at::Tensor> debug_mx8_quantize_blocks(
     const at::Tensor& x, int64_t nblocks, int64_t rows, int64_t row_elems,
     const c10::optional<at::Tensor>& payload_out,
     const c10::optional<at::Tensor>& scales_out);
+// flat contiguous x seen as [rows, S, after]; segment p = mx8_quantize of the
+// contiguous xs[:, displ_p : displ_p + counts[p], :], xs = x gathered through
+// `order` along the slice axis if given -> (payload [32*sum G_p], scales
+// [sum G_p]): the pairwise all-to-all head. With payload_out / scales_out
+// (flat uint8) the results alias their heads.
+std::tuple<at::Tensor, at::Tensor> debug_mx8_quantize_segments(
+    const at::Tensor& x, int64_t rows, int64_t after,
+    std::vector<int64_t> counts, const c10::optional<at::Tensor>& order,
+    const c10::optional<at::Tensor>& payload_out,
+    const c10::optional<at::Tensor>& scales_out);
+// the pairwise all-to-all tail: the segments' streams -> [rows, R, after] of
+// dtype, R = sum(counts), received slice i at slice order[i] if an order is
+// given. With `out` (flat, of dtype) the result aliases its head and slices
+// the order does not name keep their contents.
+at::Tensor debug_mx8_dequantize_segments(
+    const at::Tensor& payload, const at::Tensor& scales, int64_t rows,
+    int64_t after, std::vector<int64_t> counts, at::ScalarType dtype,
+    const c10::optional<at::Tensor>& order,
+    const c10::optional<at::Tensor>& out);
 // staging: flat P rank-major blocks of [rows, row_elems]; out: contiguous
 // [rows, P, row_elems]. The axis unpack of an equal-count Allgather.
 void debug_unpack_blocks(const at::Tensor& staging, const at::Tensor& out);

@@ -6,10 +6,15 @@ Alltoalls whose backward routes gradients automatically. The router is
 replicated, so only ITS gradients are averaged; expert gradients stay
 rank-local by construction.
 
+--compression mxfp8 sends the tokens, and their gradients, over the
+block-scaled fp8 wire with the token permutes fused into the codec kernels
+(AlltoallPairwiseCompressed); the default run is unchanged.
+
 Run: torchrun --standalone --local-addr 127.0.0.1 --nproc-per-node 2 \
-        examples/expert_parallel_moe.py
+        examples/expert_parallel_moe.py [--compression mxfp8]
 """
 
+import argparse
 import os
 import sys
 
@@ -19,12 +24,18 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import mpi4torch_amd as m4a
 from mpi4torch_amd.models.moe import ExpertParallelMoE
 
+ap = argparse.ArgumentParser()
+ap.add_argument("--compression", choices=["mxfp8"], default=None,
+                help="send tokens over the mxfp8 wire")
+args = ap.parse_args()
+
 device = torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")
 comm = m4a.COMM_WORLD
 
 torch.manual_seed(4)  # router + this rank's experts (router identical everywhere)
 d_model, n_experts = 32, 4 * comm.size
-moe = ExpertParallelMoE(d_model, n_experts).to(device)
+moe = ExpertParallelMoE(d_model, n_experts,
+                        compression=args.compression).to(device)
 opt = torch.optim.AdamW(moe.parameters(), lr=1e-3)
 
 torch.manual_seed(500 + comm.rank)  # per-rank token stream

@@ -336,6 +336,52 @@ class MPI_Communicator:
         return self._comm.AlltoallPairwise(tensor, axis, send_counts,
                                            recv_counts)
 
+    def AlltoallPairwiseCompressed(
+            self, tensor: torch.Tensor, axis: int, send_counts: List[int],
+            recv_counts: List[int],
+            send_order: Optional[torch.Tensor] = None,
+            recv_order: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Pairwise-count alltoall along ``axis`` that travels as
+        block-scaled fp8, with the slice permutes fused into the codec
+        (MI355X extension): the expert-parallel dispatch/combine primitive
+        over the mxfp8 wire.
+
+        Counts work as in AlltoallPairwise: this rank sends
+        ``send_counts[j]`` slices to rank j, their sum is the axis size,
+        zeros are allowed and ``recv_counts=[]`` has them exchanged
+        automatically. With ``send_order`` the slices are first gathered,
+        ``xs = tensor.index_select(axis, send_order)``; block j of ``xs``
+        (float32, bfloat16 or float16) is quantized to mxfp8 in groups of 32
+        consecutive elements of the contiguous block that start at its first
+        element, payload and scale bytes travel in one grouped exchange, and
+        the received blocks are dequantized in rank order into ``y``. With
+        ``recv_order`` the result is ``out.index_copy_(axis, recv_order,
+        y)``: received slice i lands at slice ``recv_order[i]``. Neither
+        permute is a pass of its own: a fused gfx950 kernel gathers the
+        slices while it quantizes and a second one scatters them while it
+        dequantizes. There is no reduction, so every value is quantized
+        exactly once; the own block goes through the codec like every
+        other. A non-finite value turns the group of 32 that holds it into
+        NaN on the rank that receives it.
+
+        ``send_order`` and ``recv_order`` are 1-D int64 tensors on the
+        tensor's device whose lengths are the two count sums; each must be a
+        permutation. That is checked for CPU tensors, and for GPU tensors
+        only under MPI4TORCH_AMD_DEBUG=1 (the check costs a sync); the GPU
+        kernels read an out-of-range entry as a slice of zeros and drop it
+        on the receiving side, so a bad index never leaves the tensor.
+
+        A world of one returns the exact permutation: nothing crosses a
+        wire, so nothing is compressed.
+
+        Backward: AlltoallPairwiseCompressed of the gradient with the counts
+        and the orders swapped — the exact adjoint of gather, exchange and
+        scatter; quantization is straight-through and the gradient itself
+        travels compressed.
+        """
+        return self._comm.AlltoallPairwiseCompressed(
+            tensor, axis, send_counts, recv_counts, send_order, recv_order)
+
     def Iallreduce(self, tensor: torch.Tensor, op: int) -> WaitHandle:
         """Non-blocking Allreduce (no autograd): returns a WaitHandle whose
         Wait() yields the reduced tensor. The overlap primitive behind

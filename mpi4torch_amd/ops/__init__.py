@@ -87,6 +87,17 @@ def alltoall_pairwise(tensor: torch.Tensor, axis: int, send_counts,
         [] if recv_counts is None else list(recv_counts))
 
 
+def alltoall_pairwise_compressed(tensor: torch.Tensor, axis: int, send_counts,
+                                 recv_counts=None, send_order=None,
+                                 recv_order=None, comm=None):
+    """Pairwise-count all-to-all over an mxfp8 wire, with the optional slice
+    permutes fused into the codec kernels."""
+    return _comm(comm).AlltoallPairwiseCompressed(
+        tensor, axis, list(send_counts),
+        [] if recv_counts is None else list(recv_counts),
+        send_order, recv_order)
+
+
 def iallreduce(tensor: torch.Tensor, op: Optional[int] = None, comm=None):
     return _comm(comm).Iallreduce(tensor, _m.MPI_SUM if op is None else op)
 

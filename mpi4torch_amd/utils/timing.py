@@ -61,6 +61,17 @@ def alltoall_compressed_wire_bytes(numel: int, world: int) -> int:
     return (world - 1) * 33 * ((block + 31) // 32)
 
 
+def mxfp8_alltoall_pairwise_wire_bytes(send_counts, slice_elems: int,
+                                       rank: int) -> int:
+    """Bytes rank ``rank`` sends in AlltoallPairwiseCompressed:
+    ``send_counts[p]`` slices of ``slice_elems`` elements (the product of
+    every dimension but the axis) to each other rank p, each block quantized
+    on its own (33 bytes per group of 32, the partial last group padded).
+    The block that stays local is not counted."""
+    return sum(33 * ((c * slice_elems + 31) // 32)
+               for p, c in enumerate(send_counts) if p != rank)
+
+
 class CollectiveTimer:
     """Times GPU regions with CUDA/HIP events (no host sync until query)."""
 

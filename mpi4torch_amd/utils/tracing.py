@@ -158,6 +158,15 @@ class TracedCommunicator:
             lambda: self._comm.AlltoallPairwise(tensor, axis, send_counts,
                                                 recv_counts))
 
+    def AlltoallPairwiseCompressed(self, tensor, axis, send_counts,
+                                   recv_counts, send_order=None,
+                                   recv_order=None):
+        return self._record(
+            "AlltoallPairwiseCompressed", tensor,
+            lambda: self._comm.AlltoallPairwiseCompressed(
+                tensor, axis, send_counts, recv_counts, send_order,
+                recv_order))
+
     def Iallreduce(self, tensor, op):
         return self._record("Iallreduce", tensor,
                             lambda: self._comm.Iallreduce(tensor, op))

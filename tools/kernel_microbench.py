@@ -9,6 +9,7 @@ reported GB/s counts actual bytes touched. Run on an MI355X box:
     python tools/kernel_microbench.py --mx8-reduce-to   # only that part
     python tools/kernel_microbench.py --mx8-dequantize-blocks   # only that part
     python tools/kernel_microbench.py --mx8-quantize-blocks     # only that part
+    python tools/kernel_microbench.py --mx8-segments            # only that part
 
 The mxfp8 section times the three codec kernels and, in the same run and
 alternating with it, the sibling fp8_reduce kernel at the same P and n, so
@@ -19,7 +20,9 @@ The dequantize-blocks part does the same for the fused allgather tail
 mx8_dequantize_blocks against P x mx8_dequantize into staging plus the slab
 unpack that Allgather uses. The quantize-blocks part does the same for the
 fused all-to-all head mx8_quantize_blocks against the axis pack into staging
-plus mx8_quantize.
+plus mx8_quantize. The segments part does the same for the pairwise
+all-to-all head and tail with a fused token permute, mx8_quantize_segments
+and mx8_dequantize_segments, against index_select plus the flat codec kernel.
 """
 
 import os
@@ -383,6 +386,137 @@ def mx8_quantize_blocks_section(repeats=5):
     line("w1 full-path Alltoall", ta, t.numel() * 2)
 
 
+def mx8_segments_section(repeats=5):
+    """mx8_quantize_segments / mx8_dequantize_segments at the MoE token
+    geometry, 128Ki tokens x 4096, P = 8 segments of uneven counts (one of
+    them zero), bf16 and fp32, against the sequences they replace,
+    alternating in the same run:
+      send  index_select(0, order) + ONE flat mx8_quantize   vs the fused
+            head reading tokens through the index;
+      recv  ONE flat mx8_dequantize + index_select(0, inverse)   vs the
+            fused tail writing tokens through the index;
+      flat  the no-index segments launchers vs the flat kernels (every L_p
+            is a multiple of 32 here, so they dispatch to those kernels).
+    A row is 4096 elements, so every segment is a whole number of groups and
+    the sequence's bytes are byte for byte the fused kernels'. One launch
+    touches 1 GiB (bf16) or 2 GiB (fp32) of tokens plus 528 MiB of codec
+    bytes, past the 256 MiB Infinity Cache. Bytes of a fused kernel:
+    N*D*esize + 33*N*D/32 (+ 8N of index); the sequence moves N*D*esize
+    twice more."""
+    C = m._C
+    med = lambda v: sorted(v)[len(v) // 2]
+
+    def line(name, times, nbytes):
+        t = med(times)
+        print(f"{name:44s} {t*1e3:9.1f} us  {nbytes/t/1e9:6.2f} TB/s  "
+              f"(min {min(times)*1e3:.1f} max {max(times)*1e3:.1f} us, "
+              f"{len(times)} repeats)", flush=True)
+        return t
+
+    def versus(tag, seq_name, seq, seq_b, fused_name, fused, fused_b,
+               same_kernel=False):
+        t_seq, t_fused = [], []
+        for _ in range(repeats):
+            t_seq.append(timeit(seq))
+            t_fused.append(timeit(fused))
+        a = line(f"({tag}) {seq_name}", t_seq, seq_b)
+        b = line(f"({tag}) {fused_name}", t_fused, fused_b)
+        spread = (max(t_seq) - min(t_seq)) / med(t_seq)
+        if same_kernel:
+            inside = min(t_seq) <= b <= max(t_seq)
+            verdict = ("inside the sequence min-max" if inside
+                       else "OUTSIDE the sequence min-max")
+        else:
+            verdict = ("below the sequence minimum" if b < min(t_seq)
+                       else "NOT below the sequence minimum")
+        print(f"({tag}) fused / sequence time ratio {b/a:.3f} (sequence "
+              f"min-max spread {spread*100:.1f}% of its median; fused median "
+              f"{verdict}; fused min-max "
+              f"{min(t_fused)*1e3:.1f}-{max(t_fused)*1e3:.1f} us)",
+              flush=True)
+
+    N, D = 128 << 10, 4096
+    counts = [20000, 0, 12000, 24000, 8000, 30000, 17072, 20000]
+    assert sum(counts) == N and len(counts) == P
+    gen = torch.Generator(device="cuda").manual_seed(7)
+    order = torch.randperm(N, device="cuda", generator=gen)
+    inverse = torch.empty_like(order)
+    inverse[order] = torch.arange(N, device="cuda")
+    for dtype, tag in ((torch.bfloat16, "bf16"), (torch.float32, "fp32")):
+        x = torch.randn(N, D, device="cuda") * 0.2
+        x.mul_(torch.rand(N, 1, device="cuda"))
+        x = x.to(dtype)
+        es = x.element_size()
+        flat = x.view(-1)
+        codec_b = 33 * (N * D // 32)
+        fused_b = N * D * es + codec_b
+        pay, sc = C._mx8_quantize(flat)
+
+        versus(f"send {tag}", "index_select + 1 x mx8_quantize",
+               lambda: C._mx8_quantize(x.index_select(0, order).view(-1)),
+               fused_b + 2 * N * D * es,
+               "mx8_quantize_segments, indexed",
+               lambda: C._mx8_quantize_segments(flat, 1, D, counts,
+                                                order=order),
+               fused_b + 8 * N)
+        versus(f"recv {tag}", "1 x mx8_dequantize + index_select",
+               lambda: C._mx8_dequantize(pay, sc, N * D, dtype)
+               .view(N, D).index_select(0, inverse),
+               fused_b + 2 * N * D * es,
+               "mx8_dequantize_segments, indexed",
+               lambda: C._mx8_dequantize_segments(pay, sc, 1, D, counts,
+                                                  dtype, order=order),
+               fused_b + 8 * N)
+        versus(f"flat-q {tag}", "1 x mx8_quantize",
+               lambda: C._mx8_quantize(flat), fused_b,
+               "mx8_quantize_segments, no index",
+               lambda: C._mx8_quantize_segments(flat, 1, D, counts), fused_b,
+               same_kernel=True)
+        versus(f"flat-d {tag}", "1 x mx8_dequantize",
+               lambda: C._mx8_dequantize(pay, sc, N * D, dtype), fused_b,
+               "mx8_dequantize_segments, no index",
+               lambda: C._mx8_dequantize_segments(pay, sc, 1, D, counts,
+                                                  dtype), fused_b,
+               same_kernel=True)
+        del x, flat, pay, sc
+
+    # informational: codec overhead at world size 1 (no wire at this size).
+    comm = m.COMM_WORLD
+    t = torch.randn(32768, 4096, device="cuda").to(torch.bfloat16)
+    cnt = [t.size(0)]
+    C.force_full_path(True)
+    try:
+        tc = [timeit(lambda: comm.AlltoallPairwiseCompressed(t, 0, cnt, cnt),
+                     iters=10) for _ in range(3)]
+        ta = [timeit(lambda: comm.AlltoallPairwise(t, 0, cnt, cnt), iters=10)
+              for _ in range(3)]
+        line("w1 full-path AlltoallPairwiseCompressed", tc, t.numel() * 2)
+        line("w1 full-path AlltoallPairwise", ta, t.numel() * 2)
+        del t
+        from mpi4torch_amd.models.moe import ExpertParallelMoE
+
+        tok = torch.randn(16384, 1024, device="cuda").to(torch.bfloat16)
+        for comp in (None, "mxfp8"):
+            torch.manual_seed(3)
+            layer = ExpertParallelMoE(1024, 8, compression=comp)
+            layer = layer.to(device="cuda", dtype=torch.bfloat16)
+
+            def step():
+                layer.zero_grad(set_to_none=True)
+                layer(tok).float().pow(2).sum().backward()
+
+            ts = [timeit(step, iters=5, warmup=2) for _ in range(3)]
+            line(f"w1 full-path MoE fwd+bwd compression={comp}", ts,
+                 tok.numel() * 2)
+    finally:
+        C.force_full_path(False)
+
+
+if "--mx8-segments" in sys.argv:
+    mx8_segments_section()
+    dist.destroy_process_group()
+    sys.exit(0)
+
 if "--mx8-quantize-blocks" in sys.argv:
     mx8_quantize_blocks_section()
     dist.destroy_process_group()
@@ -403,6 +537,7 @@ if "--mx8" in sys.argv:
     mx8_reduce_to_section()
     mx8_dequantize_blocks_section()
     mx8_quantize_blocks_section()
+    mx8_segments_section()
     dist.destroy_process_group()
     sys.exit(0)
 
@@ -467,5 +602,6 @@ mx8_section()
 mx8_reduce_to_section()
 mx8_dequantize_blocks_section()
 mx8_quantize_blocks_section()
+mx8_segments_section()
 
 dist.destroy_process_group()
