@@ -49,9 +49,23 @@
 // 16-byte chunks (see there); quantize_blocks has a one-thread-per-group twin
 // with element-wise index mapping; the segments kernels have
 // one-thread-per-group twins on both sides.
+//
+// What the kernels share is written once:
+//   quant_lane / dequant_lane : one lane's part of a group in the vector
+//                kernels of either direction (flat, _blocks, _segments);
+//   quantize_stream / dequantize_stream : the vector body of the _blocks and
+//                _segments kernels, templated on the map from a stream chunk
+//                to its place in the tensor (BlockMap, SegMap); the kernels
+//                themselves only pick the stream that grid.y names;
+//   sum_copies : the rank-order sum of reduce and reduce_to;
+//   SegCursor  : the (b, c, a) walk of the two segments twins.
+// On the host, by_dtype / by_width / by_width_mode turn the run-time dtype,
+// index width and segment mode into template arguments, grid2d is the capped
+// 2-D grid, and launch_segments_t is both segments launchers.
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp8.h>
+#include <type_traits>
 #include "kernels.hpp"
 
 namespace m4a {
@@ -249,6 +263,125 @@ __device__ inline void dequant_group_scalar(
   }
 }
 
+// ---- vector lane routines -------------------------------------------------
+//
+// The quantize/dequantize family's lane layout: a lane owns one 16-byte
+// chunk of the tensor side, EPL elements, and the EPL payload bytes that go
+// with it; LPG lanes share a group.
+template <int K> constexpr int kLPG = K == kF32 ? 8 : 4;  // lanes per group
+template <int K> constexpr int kEPL = 32 / kLPG<K>;       // elements per lane
+
+// Lane slot j's BPL payload bytes as dwords, one nontemporal load.
+template <int BPL>
+__device__ inline void load_payload(const u8* __restrict__ pin, long long j,
+                                    unsigned (&w)[BPL / 4]) {
+  if constexpr (BPL == 4) {
+    w[0] =
+        __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(pin) + j);
+  } else if constexpr (BPL == 8) {
+    const v2u t =
+        __builtin_nontemporal_load(reinterpret_cast<const v2u*>(pin) + j);
+    w[0] = t[0];
+    w[1] = t[1];
+  } else {
+    const v4u t =
+        __builtin_nontemporal_load(reinterpret_cast<const v4u*>(pin) + j);
+    for (int d = 0; d < 4; ++d) w[d] = t[d];
+  }
+}
+
+// 16-byte chunk `src` of the tensor as this lane's elements; zeros when the
+// lane has nothing to read.
+template <int K>
+__device__ inline void load_chunk(const void* __restrict__ in, long long src,
+                                  bool ok, float (&x)[kEPL<K>]) {
+  if (ok) {
+    const v4u w =
+        __builtin_nontemporal_load(reinterpret_cast<const v4u*>(in) + src);
+    unpack16<K, kEPL<K>>(w, x);
+  } else {
+    for (int k = 0; k < kEPL<K>; ++k) x[k] = 0.0f;
+  }
+}
+
+// One lane of a group's quantization. The amax crosses the group's LPG lanes
+// by xor-shuffles, so every lane of the wave must call this; a lane that
+// stores writes its EPL payload bytes at lane slot i of `pay`. Returns the
+// group's scale byte.
+template <int K>
+__device__ inline int quant_lane(const float (&x)[kEPL<K>], bool store,
+                                 u8* __restrict__ pay, long long i) {
+  constexpr int EPL = kEPL<K>;
+  unsigned a = amax_bits_of(x);
+  for (int m = 1; m < kLPG<K>; m <<= 1) {
+    const unsigned o = (unsigned)__shfl_xor((int)a, m);
+    a = o > a ? o : a;
+  }
+  int E;
+  const int sb = mx8_scale_byte(a, &E);
+  if (store) {
+    const unsigned lo = sb == 255 ? 0u : quant4(x[0], x[1], x[2], x[3], E);
+    if constexpr (K == kF32) {
+      __builtin_nontemporal_store(lo, reinterpret_cast<unsigned*>(pay) + i);
+    } else {
+      v2u o;
+      o[0] = lo;
+      o[1] = sb == 255
+                 ? 0u
+                 : quant4(x[EPL - 4], x[EPL - 3], x[EPL - 2], x[EPL - 1], E);
+      __builtin_nontemporal_store(o, reinterpret_cast<v2u*>(pay) + i);
+    }
+  }
+  return sb;
+}
+
+// One lane of a group's dequantization: the EPL payload bytes at lane slot i
+// of `pay` under scale byte sb, as the 16-byte chunk of the output dtype.
+template <int K>
+__device__ inline v4u dequant_lane(const u8* __restrict__ pay, long long i,
+                                   int sb) {
+  constexpr int EPL = kEPL<K>;
+  unsigned w[EPL / 4];
+  load_payload<EPL>(pay, i, w);
+  float x[EPL];
+  for (int d = 0; d < EPL / 4; ++d) {
+    for (int k = 0; k < 4; ++k) {
+      x[4 * d + k] = mx8_dequant((u8)(w[d] >> (8 * k)), sb);
+    }
+  }
+  return pack16<K, EPL>(x);
+}
+
+// Lane slot j of group g summed over the P copies (copy r's lane slots start
+// at r*cstride, its scales at r*G): copy 0 assigned, copies 1..P-1 added in
+// rank order on dequantized values. Returns whether any copy's group is 255.
+template <int BPL>
+__device__ inline bool sum_copies(const u8* __restrict__ pin,
+                                  const u8* __restrict__ sin, long long j,
+                                  long long cstride, long long g, long long G,
+                                  long long nranks, float (&acc)[BPL]) {
+  bool bad = false;
+  auto copy = [&](long long r, auto first) {
+    unsigned w[BPL / 4];
+    load_payload<BPL>(pin, r * cstride + j, w);
+    const int sb = sin[r * G + g];
+    bad = bad || sb == 255;
+    for (int d = 0; d < BPL / 4; ++d) {
+      for (int k = 0; k < 4; ++k) {
+        const float v = ldexpf(e4m3_to_f32((u8)(w[d] >> (8 * k))), sb - 127);
+        if constexpr (decltype(first)::value) {
+          acc[4 * d + k] = v;
+        } else {
+          acc[4 * d + k] += v;
+        }
+      }
+    }
+  };
+  copy(0, std::true_type{});
+  for (long long r = 1; r < nranks; ++r) copy(r, std::false_type{});
+  return bad;
+}
+
 // ---- quantize -----------------------------------------------------------
 
 template <int K>
@@ -256,44 +389,19 @@ __global__ __launch_bounds__(256) void mx8_quantize_kernel(
     const void* __restrict__ in, u8* __restrict__ pay, u8* __restrict__ sc,
     long long nfull, long long N) {
   using T = typename Elem<K>::type;
-  constexpr int LPG = K == kF32 ? 8 : 4;  // lanes per group
-  constexpr int EPL = 32 / LPG;           // elements per lane (16 B)
+  constexpr int LPG = kLPG<K>;
   const long long total = nfull * LPG;
   const long long stride = (long long)gridDim.x * blockDim.x;
   const int lane = threadIdx.x & 63;
-  // wave-uniform trip count: the shuffles below need every lane present
+  // wave-uniform trip count: the shuffles in quant_lane and store_scales
+  // need every lane present
   for (long long i0 = (long long)blockIdx.x * blockDim.x + (threadIdx.x & ~63);
        i0 < total; i0 += stride) {
     const long long i = i0 + lane;
     const bool act = i < total;
-    float x[EPL];
-    if (act) {
-      const v4u w =
-          __builtin_nontemporal_load(reinterpret_cast<const v4u*>(in) + i);
-      unpack16<K, EPL>(w, x);
-    } else {
-      for (int k = 0; k < EPL; ++k) x[k] = 0.0f;
-    }
-    unsigned a = amax_bits_of(x);
-    for (int m = 1; m < LPG; m <<= 1) {
-      const unsigned o = (unsigned)__shfl_xor((int)a, m);
-      a = o > a ? o : a;
-    }
-    int E;
-    const int sb = mx8_scale_byte(a, &E);
-    if (act) {
-      if constexpr (K == kF32) {
-        const unsigned o = sb == 255 ? 0u : quant4(x[0], x[1], x[2], x[3], E);
-        __builtin_nontemporal_store(o, reinterpret_cast<unsigned*>(pay) + i);
-      } else {
-        v2u o;
-        o[0] = sb == 255 ? 0u : quant4(x[0], x[1], x[2], x[3], E);
-        o[1] = sb == 255
-                   ? 0u
-                   : quant4(x[EPL - 4], x[EPL - 3], x[EPL - 2], x[EPL - 1], E);
-        __builtin_nontemporal_store(o, reinterpret_cast<v2u*>(pay) + i);
-      }
-    }
+    float x[kEPL<K>];
+    load_chunk<K>(in, i, act, x);
+    const int sb = quant_lane<K>(x, act, pay, i);
     store_scales<LPG>(sc, i0 / LPG, nfull, sb, lane);
   }
   // zero-padded partial last group
@@ -331,33 +439,10 @@ __global__ __launch_bounds__(256) void mx8_reduce_kernel(
        i0 < total; i0 += stride) {
     const long long i = i0 + lane;
     const bool act = i < total;
-    const long long g = i >> 1;
     float acc[16];
     bool bad = false;
     if (act) {
-      const v4u* base = reinterpret_cast<const v4u*>(pin);
-      {
-        const v4u w = __builtin_nontemporal_load(base + i);
-        const int sb = sin[g];
-        bad = sb == 255;
-        for (int d = 0; d < 4; ++d) {
-          for (int k = 0; k < 4; ++k) {
-            acc[4 * d + k] =
-                ldexpf(e4m3_to_f32((u8)(w[d] >> (8 * k))), sb - 127);
-          }
-        }
-      }
-      for (long long r = 1; r < nranks; ++r) {
-        const v4u w = __builtin_nontemporal_load(base + r * total + i);
-        const int sb = sin[r * n + g];
-        bad = bad || sb == 255;
-        for (int d = 0; d < 4; ++d) {
-          for (int k = 0; k < 4; ++k) {
-            acc[4 * d + k] +=
-                ldexpf(e4m3_to_f32((u8)(w[d] >> (8 * k))), sb - 127);
-          }
-        }
-      }
+      bad = sum_copies<16>(pin, sin, i, total, i >> 1, n, nranks, acc);
     } else {
       for (int k = 0; k < 16; ++k) acc[k] = 0.0f;
     }
@@ -415,30 +500,12 @@ __global__ __launch_bounds__(256) void mx8_dequantize_kernel(
     const u8* __restrict__ pay, const u8* __restrict__ sc,
     void* __restrict__ out, long long nfull, long long N) {
   using T = typename Elem<K>::type;
-  constexpr int LPG = K == kF32 ? 8 : 4;
-  constexpr int EPL = 32 / LPG;
+  constexpr int LPG = kLPG<K>;
   const long long total = nfull * LPG;
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
        i < total; i += stride) {
-    const int sb = sc[i / LPG];
-    unsigned w[EPL / 4];
-    if constexpr (K == kF32) {
-      w[0] = __builtin_nontemporal_load(
-          reinterpret_cast<const unsigned*>(pay) + i);
-    } else {
-      const v2u t =
-          __builtin_nontemporal_load(reinterpret_cast<const v2u*>(pay) + i);
-      w[0] = t[0];
-      w[EPL / 4 - 1] = t[1];
-    }
-    float x[EPL];
-    for (int d = 0; d < EPL / 4; ++d) {
-      for (int k = 0; k < 4; ++k) {
-        x[4 * d + k] = mx8_dequant((u8)(w[d] >> (8 * k)), sb);
-      }
-    }
-    __builtin_nontemporal_store(pack16<K, EPL>(x),
+    __builtin_nontemporal_store(dequant_lane<K>(pay, i, sc[i / LPG]),
                                 reinterpret_cast<v4u*>(out) + i);
   }
   // partial last group: exactly N - 32*nfull elements, nothing past N
@@ -495,21 +562,6 @@ __device__ inline void reduce_to_group_scalar(
 // the reduce kernel's width) leave each 128-byte line to four store
 // instructions and run at half the rate; one store per lane (the
 // dequantize kernel's width) keeps too few load bytes in flight.
-template <int BPL>
-__device__ inline void load_payload(const u8* __restrict__ pin, long long j,
-                                    unsigned (&w)[BPL / 4]) {
-  if constexpr (BPL == 8) {
-    const v2u t =
-        __builtin_nontemporal_load(reinterpret_cast<const v2u*>(pin) + j);
-    w[0] = t[0];
-    w[1] = t[1];
-  } else {
-    const v4u t =
-        __builtin_nontemporal_load(reinterpret_cast<const v4u*>(pin) + j);
-    for (int d = 0; d < 4; ++d) w[d] = t[d];
-  }
-}
-
 template <int K>
 __global__ __launch_bounds__(256) void mx8_reduce_to_kernel(
     const u8* __restrict__ pin, const u8* __restrict__ sin,
@@ -520,39 +572,13 @@ __global__ __launch_bounds__(256) void mx8_reduce_to_kernel(
   constexpr int NS = 2;                           // 16-byte stores per lane
   constexpr int BPL = NS * EPS;                   // payload bytes per lane
   constexpr int LPG = 32 / BPL;                   // lanes per group
-  constexpr int DW = BPL / 4;                     // payload dwords per lane
   const long long total = nfull * LPG;            // lane slots in the body
-  const long long cstride = G * LPG;              // lane slots per copy
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
        i < total; i += stride) {
-    const long long g = i / LPG;
     float acc[BPL];
-    bool bad;
-    {
-      unsigned w[DW];
-      load_payload<BPL>(pin, i, w);
-      const int sb = sin[g];
-      bad = sb == 255;
-      for (int d = 0; d < DW; ++d) {
-        for (int k = 0; k < 4; ++k) {
-          acc[4 * d + k] =
-              ldexpf(e4m3_to_f32((u8)(w[d] >> (8 * k))), sb - 127);
-        }
-      }
-    }
-    for (long long r = 1; r < nranks; ++r) {
-      unsigned w[DW];
-      load_payload<BPL>(pin, r * cstride + i, w);
-      const int sb = sin[r * G + g];
-      bad = bad || sb == 255;
-      for (int d = 0; d < DW; ++d) {
-        for (int k = 0; k < 4; ++k) {
-          acc[4 * d + k] +=
-              ldexpf(e4m3_to_f32((u8)(w[d] >> (8 * k))), sb - 127);
-        }
-      }
-    }
+    const bool bad =
+        sum_copies<BPL>(pin, sin, i, G * LPG, i / LPG, G, nranks, acc);
     v4u* o = reinterpret_cast<v4u*>(out) + i * NS;
     for (int s = 0; s < NS; ++s) {
       float x[EPS];
@@ -585,6 +611,79 @@ __global__ __launch_bounds__(256) void mx8_reduce_to_kernel_scalar(
   }
 }
 
+// ---- mapped streams (the bodies of the _blocks and _segments kernels) -----
+//
+// One mxfp8 stream (payload base bp, scales base bs; grid.y picked it, so
+// both are wave-uniform) whose 16-byte chunks lie scattered in the tensor:
+// map(i) is the tensor's chunk index of stream chunk i, or, where
+// Map::kCanMiss, -1 for a chunk that has no place there. I is the index
+// type of the per-lane arithmetic, 32 bits whenever the stream has fewer
+// than 2^31 lane slots. The grid-stride loop's two arguments, the thread's
+// first index and the stride, are formed in the kernel: the compiler reads
+// the launch dimensions as scalar kernel arguments only in the __global__
+// function itself (read here they cost a vector load and 2 to 8 VGPRs).
+#define MX8_GRID_STRIDE(I) \
+  (I) blockIdx.x * blockDim.x + threadIdx.x, (I)gridDim.x * blockDim.x
+
+// Chunk i of block r of a contiguous [rows][nblocks][cpr chunks] tensor: one
+// division by the row length.
+template <typename I>
+struct BlockMap {
+  static constexpr bool kCanMiss = false;
+  long long r, nblocks;
+  I cpr;
+  __device__ long long operator()(I i) const {
+    const I row = i / cpr;
+    const I col = i - row * cpr;
+    return ((long long)row * nblocks + r) * (long long)cpr + (long long)col;
+  }
+};
+
+// The quantize kernel's lane layout over ALL `slots` = G*LPG lane slots of
+// the stream (wave-uniform trip count: the shuffles and the scale gather
+// need every lane). Slots from `chunks` on and missed chunks load nothing,
+// count as zeros in the amax and store zero payload, so the partial last
+// group needs no scalar tail. bs has any alignment: store_scales falls back
+// to per-lane bytes.
+template <int K, typename I, typename Map>
+__device__ inline void quantize_stream(const void* __restrict__ in,
+                                       u8* __restrict__ bp,
+                                       u8* __restrict__ bs, long long G,
+                                       I chunks, I slots, const Map& map,
+                                       I first, I stride) {
+  constexpr int LPG = kLPG<K>;
+  const int lane = threadIdx.x & 63;
+  // i0: the wave's first slot (workgroups are whole waves)
+  for (I i0 = first & ~(I)63; i0 < slots; i0 += stride) {
+    const I i = i0 + lane;
+    long long src = -1;
+    if (i < chunks) src = map(i);
+    float x[kEPL<K>];
+    load_chunk<K>(in, src, Map::kCanMiss ? src >= 0 : i < chunks, x);
+    const int sb = quant_lane<K>(x, i < slots, bp, (long long)i);
+    store_scales<LPG>(bs, (long long)(i0 / LPG), G, sb, lane);
+  }
+}
+
+// The dequantize kernel's lane layout over all `chunks` whole chunks of the
+// stream, so nothing past its last element is written; the padded payload
+// keeps the last group's loads inside the stream. A missed chunk is skipped.
+template <int K, typename I, typename Map>
+__device__ inline void dequantize_stream(const u8* __restrict__ bp,
+                                         const u8* __restrict__ bs,
+                                         void* __restrict__ out, I chunks,
+                                         const Map& map, I first, I stride) {
+  for (I i = first; i < chunks; i += stride) {
+    const long long dst = map(i);
+    if constexpr (Map::kCanMiss) {
+      if (dst < 0) continue;
+    }
+    __builtin_nontemporal_store(
+        dequant_lane<K>(bp, (long long)i, bs[i / kLPG<K>]),
+        reinterpret_cast<v4u*>(out) + dst);
+  }
+}
+
 // ---- dequantize_blocks (the allgather tail) ------------------------------
 //
 // nblocks mxfp8 streams of L = rows*row_elems elements each (groups start at
@@ -608,38 +707,9 @@ __global__ __launch_bounds__(256) void mx8_dequantize_blocks_kernel(
     const u8* __restrict__ pay, const u8* __restrict__ sc,
     void* __restrict__ out, long long Gb, I chunks, I cpr,
     long long nblocks) {
-  constexpr int LPG = K == kF32 ? 8 : 4;
-  constexpr int EPL = 32 / LPG;
   const long long r = blockIdx.y;
-  const u8* __restrict__ bp = pay + r * Gb * 32;
-  const u8* __restrict__ bs = sc + r * Gb;
-  const I stride = (I)gridDim.x * blockDim.x;
-  for (I i = (I)blockIdx.x * blockDim.x + threadIdx.x; i < chunks;
-       i += stride) {
-    const int sb = bs[i / LPG];
-    unsigned w[EPL / 4];
-    if constexpr (K == kF32) {
-      w[0] = __builtin_nontemporal_load(
-          reinterpret_cast<const unsigned*>(bp) + i);
-    } else {
-      const v2u t =
-          __builtin_nontemporal_load(reinterpret_cast<const v2u*>(bp) + i);
-      w[0] = t[0];
-      w[EPL / 4 - 1] = t[1];
-    }
-    float x[EPL];
-    for (int d = 0; d < EPL / 4; ++d) {
-      for (int k = 0; k < 4; ++k) {
-        x[4 * d + k] = mx8_dequant((u8)(w[d] >> (8 * k)), sb);
-      }
-    }
-    const I row = i / cpr;
-    const I col = i - row * cpr;
-    const long long dst =
-        ((long long)row * nblocks + r) * (long long)cpr + (long long)col;
-    __builtin_nontemporal_store(pack16<K, EPL>(x),
-                                reinterpret_cast<v4u*>(out) + dst);
-  }
+  dequantize_stream<K, I>(pay + r * Gb * 32, sc + r * Gb, out, chunks,
+                          BlockMap<I>{r, nblocks, cpr}, MX8_GRID_STRIDE(I));
 }
 
 // General twin: any row length, any alignment of the payload and output
@@ -724,51 +794,9 @@ template <int K, typename I>
 __global__ __launch_bounds__(256) void mx8_quantize_blocks_kernel(
     const void* __restrict__ in, u8* __restrict__ pay, u8* __restrict__ sc,
     long long Gb, I chunks, I cpr, I slots, long long nblocks) {
-  constexpr int LPG = K == kF32 ? 8 : 4;
-  constexpr int EPL = 32 / LPG;
   const long long r = blockIdx.y;
-  u8* __restrict__ bp = pay + r * Gb * 32;
-  u8* __restrict__ bs = sc + r * Gb;
-  const I stride = (I)gridDim.x * blockDim.x;
-  const int lane = threadIdx.x & 63;
-  // wave-uniform trip count: the shuffles below need every lane present
-  for (I i0 = (I)blockIdx.x * blockDim.x + (threadIdx.x & ~63); i0 < slots;
-       i0 += stride) {
-    const I i = i0 + lane;
-    float x[EPL];
-    if (i < chunks) {
-      const I row = i / cpr;
-      const I col = i - row * cpr;
-      const long long src =
-          ((long long)row * nblocks + r) * (long long)cpr + (long long)col;
-      const v4u w =
-          __builtin_nontemporal_load(reinterpret_cast<const v4u*>(in) + src);
-      unpack16<K, EPL>(w, x);
-    } else {
-      for (int k = 0; k < EPL; ++k) x[k] = 0.0f;
-    }
-    unsigned a = amax_bits_of(x);
-    for (int m = 1; m < LPG; m <<= 1) {
-      const unsigned o = (unsigned)__shfl_xor((int)a, m);
-      a = o > a ? o : a;
-    }
-    int E;
-    const int sb = mx8_scale_byte(a, &E);
-    if (i < slots) {
-      if constexpr (K == kF32) {
-        const unsigned o = sb == 255 ? 0u : quant4(x[0], x[1], x[2], x[3], E);
-        __builtin_nontemporal_store(o, reinterpret_cast<unsigned*>(bp) + i);
-      } else {
-        v2u o;
-        o[0] = sb == 255 ? 0u : quant4(x[0], x[1], x[2], x[3], E);
-        o[1] = sb == 255
-                   ? 0u
-                   : quant4(x[EPL - 4], x[EPL - 3], x[EPL - 2], x[EPL - 1], E);
-        __builtin_nontemporal_store(o, reinterpret_cast<v2u*>(bp) + i);
-      }
-    }
-    store_scales<LPG>(bs, (long long)(i0 / LPG), Gb, sb, lane);
-  }
+  quantize_stream<K, I>(in, pay + r * Gb * 32, sc + r * Gb, Gb, chunks, slots,
+                        BlockMap<I>{r, nblocks, cpr}, MX8_GRID_STRIDE(I));
 }
 
 // General twin: any row length, any alignment of the input and payload
@@ -832,137 +860,67 @@ struct SegArgs {
   Mx8SegDesc s[kMaxMx8SegsPerLaunch];
 };
 
+// Segment blockIdx.y of the launch as a mapped stream: cps chunks per slice,
+// cpr = count*cps per row.
 template <typename I, int MODE>
-__device__ inline long long seg_chunk(I i, long long displ,
-                                      const long long* __restrict__ idx,
-                                      long long S, I cps, I cpr) {
-  if constexpr (MODE == 0) {
-    const I row = i / cpr;
-    const I col = i - row * cpr;
-    return ((long long)row * S + displ) * (long long)cps + (long long)col;
-  } else if constexpr (MODE == 1) {
-    const I c = i / cps;
-    const I col = i - c * cps;
-    const long long t = idx[displ + (long long)c];
-    return (unsigned long long)t < (unsigned long long)S
-               ? t * (long long)cps + (long long)col
-               : -1;
-  } else {
-    const I row = i / cpr;
-    const I rem = i - row * cpr;
-    const I c = rem / cps;
-    const I col = rem - c * cps;
-    const long long t = idx[displ + (long long)c];
-    return (unsigned long long)t < (unsigned long long)S
-               ? ((long long)row * S + t) * (long long)cps + (long long)col
-               : -1;
+struct SegMap {
+  static constexpr bool kCanMiss = true;
+  long long displ, goff;
+  const long long* __restrict__ idx;
+  long long S;
+  I cps, cpr, chunks;
+  __device__ SegMap(const Mx8SegDesc& d, const long long* idx, long long S,
+                    I cps, long long rows)
+      : displ(d.displ), goff(d.goff), idx(idx), S(S), cps(cps),
+        cpr((I)d.count * cps), chunks((I)rows * cpr) {}
+  __device__ long long operator()(I i) const {
+    if constexpr (MODE == 0) {
+      const I row = i / cpr;
+      const I col = i - row * cpr;
+      return ((long long)row * S + displ) * (long long)cps + (long long)col;
+    } else if constexpr (MODE == 1) {
+      const I c = i / cps;
+      const I col = i - c * cps;
+      const long long t = idx[displ + (long long)c];
+      return (unsigned long long)t < (unsigned long long)S
+                 ? t * (long long)cps + (long long)col
+                 : -1;
+    } else {
+      const I row = i / cpr;
+      const I rem = i - row * cpr;
+      const I c = rem / cps;
+      const I col = rem - c * cps;
+      const long long t = idx[displ + (long long)c];
+      return (unsigned long long)t < (unsigned long long)S
+                 ? ((long long)row * S + t) * (long long)cps + (long long)col
+                 : -1;
+    }
   }
-}
+};
 
-// The quantize kernel's lane layout over ALL G_p*LPG lane slots of the
-// segment (wave-uniform trip count: the shuffles and the scale gather need
-// every lane). Slots past L_p/EPL count as zeros and store the zero padding,
-// so the partial last group needs no scalar tail. The scales base sc + goff
-// has any alignment: store_scales falls back to per-lane bytes.
+// quantize_stream over the segment's G_p*LPG lane slots.
 template <int K, typename I, int MODE>
 __global__ __launch_bounds__(256) void mx8_quantize_segments_kernel(
     const void* __restrict__ in, const long long* __restrict__ idx,
     u8* __restrict__ pay, u8* __restrict__ sc, SegArgs segs, long long S,
     I cps, long long rows) {
-  constexpr int LPG = K == kF32 ? 8 : 4;
-  constexpr int EPL = 32 / LPG;
-  const long long count = segs.s[blockIdx.y].count;
-  if (count == 0) return;
-  const long long displ = segs.s[blockIdx.y].displ;
-  const long long goff = segs.s[blockIdx.y].goff;
-  const I cpr = (I)count * cps;
-  const I chunks = (I)rows * cpr;
-  const long long G = ((long long)chunks + LPG - 1) / LPG;
-  const I slots = (I)(G * LPG);
-  u8* __restrict__ bp = pay + goff * 32;
-  u8* __restrict__ bs = sc + goff;
-  const I stride = (I)gridDim.x * blockDim.x;
-  const int lane = threadIdx.x & 63;
-  for (I i0 = (I)blockIdx.x * blockDim.x + (threadIdx.x & ~63); i0 < slots;
-       i0 += stride) {
-    const I i = i0 + lane;
-    float x[EPL];
-    long long src = -1;
-    if (i < chunks) src = seg_chunk<I, MODE>(i, displ, idx, S, cps, cpr);
-    if (src >= 0) {
-      const v4u w =
-          __builtin_nontemporal_load(reinterpret_cast<const v4u*>(in) + src);
-      unpack16<K, EPL>(w, x);
-    } else {
-      for (int k = 0; k < EPL; ++k) x[k] = 0.0f;
-    }
-    unsigned a = amax_bits_of(x);
-    for (int m = 1; m < LPG; m <<= 1) {
-      const unsigned o = (unsigned)__shfl_xor((int)a, m);
-      a = o > a ? o : a;
-    }
-    int E;
-    const int sb = mx8_scale_byte(a, &E);
-    if (i < slots) {
-      if constexpr (K == kF32) {
-        const unsigned o = sb == 255 ? 0u : quant4(x[0], x[1], x[2], x[3], E);
-        __builtin_nontemporal_store(o, reinterpret_cast<unsigned*>(bp) + i);
-      } else {
-        v2u o;
-        o[0] = sb == 255 ? 0u : quant4(x[0], x[1], x[2], x[3], E);
-        o[1] = sb == 255
-                   ? 0u
-                   : quant4(x[EPL - 4], x[EPL - 3], x[EPL - 2], x[EPL - 1], E);
-        __builtin_nontemporal_store(o, reinterpret_cast<v2u*>(bp) + i);
-      }
-    }
-    store_scales<LPG>(bs, (long long)(i0 / LPG), G, sb, lane);
-  }
+  if (segs.s[blockIdx.y].count == 0) return;
+  const SegMap<I, MODE> map(segs.s[blockIdx.y], idx, S, cps, rows);
+  const long long G = ((long long)map.chunks + kLPG<K> - 1) / kLPG<K>;
+  quantize_stream<K, I>(in, pay + map.goff * 32, sc + map.goff, G, map.chunks,
+                        (I)(G * kLPG<K>), map, MX8_GRID_STRIDE(I));
 }
 
-// The dequantize kernel's lane layout over all L_p/EPL chunks of the
-// segment: whole chunks only, so nothing past element L_p is written. The
-// padded payload keeps the last group's loads inside the segment.
+// dequantize_stream over the segment's L_p/EPL chunks.
 template <int K, typename I, int MODE>
 __global__ __launch_bounds__(256) void mx8_dequantize_segments_kernel(
     const u8* __restrict__ pay, const u8* __restrict__ sc,
     const long long* __restrict__ idx, void* __restrict__ out, SegArgs segs,
     long long S, I cps, long long rows) {
-  constexpr int LPG = K == kF32 ? 8 : 4;
-  constexpr int EPL = 32 / LPG;
-  const long long count = segs.s[blockIdx.y].count;
-  if (count == 0) return;
-  const long long displ = segs.s[blockIdx.y].displ;
-  const long long goff = segs.s[blockIdx.y].goff;
-  const I cpr = (I)count * cps;
-  const I chunks = (I)rows * cpr;
-  const u8* __restrict__ bp = pay + goff * 32;
-  const u8* __restrict__ bs = sc + goff;
-  const I stride = (I)gridDim.x * blockDim.x;
-  for (I i = (I)blockIdx.x * blockDim.x + threadIdx.x; i < chunks;
-       i += stride) {
-    const long long dst = seg_chunk<I, MODE>(i, displ, idx, S, cps, cpr);
-    if (dst < 0) continue;
-    const int sb = bs[i / LPG];
-    unsigned w[EPL / 4];
-    if constexpr (K == kF32) {
-      w[0] = __builtin_nontemporal_load(
-          reinterpret_cast<const unsigned*>(bp) + i);
-    } else {
-      const v2u t =
-          __builtin_nontemporal_load(reinterpret_cast<const v2u*>(bp) + i);
-      w[0] = t[0];
-      w[EPL / 4 - 1] = t[1];
-    }
-    float x[EPL];
-    for (int d = 0; d < EPL / 4; ++d) {
-      for (int k = 0; k < 4; ++k) {
-        x[4 * d + k] = mx8_dequant((u8)(w[d] >> (8 * k)), sb);
-      }
-    }
-    __builtin_nontemporal_store(pack16<K, EPL>(x),
-                                reinterpret_cast<v4u*>(out) + dst);
-  }
+  if (segs.s[blockIdx.y].count == 0) return;
+  const SegMap<I, MODE> map(segs.s[blockIdx.y], idx, S, cps, rows);
+  dequantize_stream<K, I>(pay + map.goff * 32, sc + map.goff, out, map.chunks,
+                          map, MX8_GRID_STRIDE(I));
 }
 
 // General twins: any slice length, any alignment of the bases (an odd
@@ -971,47 +929,79 @@ __global__ __launch_bounds__(256) void mx8_dequantize_segments_kernel(
 // (b, c, a) with two divisions and the 32 elements are walked from there,
 // the slice index reloaded whenever c changes. Token rows of an MoE layer
 // (after % EPL == 0, allocator-aligned bases) never take them.
+
+// Position (b, c, a) of a stream element of segment d and its tensor slice t.
+template <bool IDX>
+struct SegCursor {
+  const Mx8SegDesc& d;
+  const long long* __restrict__ idx;
+  long long S, after, L;  // L: elements in the segment's stream
+  long long e, b, c, a, t;
+
+  __device__ SegCursor(const Mx8SegDesc& d, const long long* idx, long long S,
+                       long long after, long long rows)
+      : d(d), idx(idx), S(S), after(after), L(rows * d.count * after) {}
+  __device__ long long slice() const {
+    return IDX ? idx[d.displ + c] : d.displ + c;
+  }
+  // to stream element e0, which must exist
+  __device__ void seek(long long e0) {
+    const long long run = d.count * after;
+    e = e0;
+    b = e0 / run;
+    const long long rem = e0 - b * run;
+    c = rem / after;
+    a = rem - c * after;
+    t = slice();
+  }
+  __device__ bool in_stream() const { return e < L; }
+  // the current element's tensor offset, or -1 when its slice index is
+  // outside [0, S)
+  __device__ long long offset() const {
+    return (unsigned long long)t < (unsigned long long)S
+               ? (b * S + t) * after + a
+               : -1;
+  }
+  // one element on; the slice index is reloaded whenever c changes, but
+  // never for an element past the stream
+  __device__ void advance() {
+    ++e;
+    if (++a == after) {
+      a = 0;
+      if (++c == d.count) {
+        c = 0;
+        ++b;
+      }
+      if (e < L) t = slice();
+    }
+  }
+};
+
 template <int K, bool IDX>
 __global__ __launch_bounds__(256) void mx8_quantize_segments_kernel_scalar(
     const void* __restrict__ in, const long long* __restrict__ idx,
     u8* __restrict__ pay, u8* __restrict__ sc, SegArgs segs, long long S,
     long long after, long long rows) {
   using T = typename Elem<K>::type;
-  const long long count = segs.s[blockIdx.y].count;
-  if (count == 0) return;
-  const long long displ = segs.s[blockIdx.y].displ;
-  const long long goff = segs.s[blockIdx.y].goff;
-  const long long run = count * after;
-  const long long L = rows * run;
-  const long long G = (L + 31) / 32;
+  const Mx8SegDesc& d = segs.s[blockIdx.y];
+  if (d.count == 0) return;
+  SegCursor<IDX> cur(d, idx, S, after, rows);
+  const long long G = (cur.L + 31) / 32;
   const T* __restrict__ src = reinterpret_cast<const T*>(in);
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < G;
        g += stride) {
-    const long long e0 = g * 32;
-    long long b = e0 / run;
-    const long long rem = e0 - b * run;
-    long long c = rem / after;
-    long long a = rem - c * after;
-    long long t = IDX ? idx[displ + c] : displ + c;
+    cur.seek(g * 32);
     float x[32];
     for (int k = 0; k < 32; ++k) {
-      if (e0 + k < L) {
-        const bool ok = (unsigned long long)t < (unsigned long long)S;
-        x[k] = ok ? elem_to_f32<K>(src[(b * S + t) * after + a]) : 0.0f;
-        if (++a == after) {
-          a = 0;
-          if (++c == count) {
-            c = 0;
-            ++b;
-          }
-          if (e0 + k + 1 < L) t = IDX ? idx[displ + c] : displ + c;
-        }
-      } else {
-        x[k] = 0.0f;
+      x[k] = 0.0f;
+      if (cur.in_stream()) {
+        const long long o = cur.offset();
+        if (o >= 0) x[k] = elem_to_f32<K>(src[o]);
+        cur.advance();
       }
     }
-    encode_group_scalar(x, pay + (goff + g) * 32, sc + goff + g);
+    encode_group_scalar(x, pay + (d.goff + g) * 32, sc + d.goff + g);
   }
 }
 
@@ -1021,40 +1011,20 @@ __global__ __launch_bounds__(256) void mx8_dequantize_segments_kernel_scalar(
     const long long* __restrict__ idx, void* __restrict__ out, SegArgs segs,
     long long S, long long after, long long rows) {
   using T = typename Elem<K>::type;
-  const long long count = segs.s[blockIdx.y].count;
-  if (count == 0) return;
-  const long long displ = segs.s[blockIdx.y].displ;
-  const long long goff = segs.s[blockIdx.y].goff;
-  const long long run = count * after;
-  const long long L = rows * run;
-  const long long G = (L + 31) / 32;
+  const Mx8SegDesc& d = segs.s[blockIdx.y];
+  if (d.count == 0) return;
+  SegCursor<IDX> cur(d, idx, S, after, rows);
+  const long long G = (cur.L + 31) / 32;
   T* __restrict__ dst = reinterpret_cast<T*>(out);
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < G;
        g += stride) {
-    const long long e0 = g * 32;
-    long long b = e0 / run;
-    const long long rem = e0 - b * run;
-    long long c = rem / after;
-    long long a = rem - c * after;
-    long long t = IDX ? idx[displ + c] : displ + c;
-    const int sb = sc[goff + g];
-    const u8* __restrict__ p = pay + (goff + g) * 32;
-    for (int k = 0; k < 32; ++k) {
-      if (e0 + k < L) {
-        if ((unsigned long long)t < (unsigned long long)S) {
-          dst[(b * S + t) * after + a] =
-              f32_to_elem<K>(mx8_dequant(p[k], sb));
-        }
-        if (++a == after) {
-          a = 0;
-          if (++c == count) {
-            c = 0;
-            ++b;
-          }
-          if (e0 + k + 1 < L) t = IDX ? idx[displ + c] : displ + c;
-        }
-      }
+    cur.seek(g * 32);
+    const int sb = sc[d.goff + g];
+    const u8* __restrict__ p = pay + (d.goff + g) * 32;
+    for (int k = 0; k < 32 && cur.in_stream(); ++k, cur.advance()) {
+      const long long o = cur.offset();
+      if (o >= 0) dst[o] = f32_to_elem<K>(mx8_dequant(p[k], sb));
     }
   }
 }
@@ -1066,14 +1036,61 @@ inline unsigned grid_for(long long work) {
   return (unsigned)blocks;
 }
 
+// grid.y carries the block or segment; grid.x is capped so the launch stays
+// near the 4096 workgroups of the flat kernels
+inline dim3 grid2d(long long work, int ny) {
+  const long long xcap = 4096 / ny > 0 ? 4096 / ny : 1;
+  long long x = (work + 255) / 256;
+  if (x > xcap) x = xcap;
+  if (x < 1) x = 1;
+  return dim3((unsigned)x, (unsigned)ny);
+}
+
 inline bool aligned(const void* p, uintptr_t a) {
   return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0;
+}
+
+template <int V> using Tag = std::integral_constant<int, V>;
+
+// f(Tag<K>) for the dtype code of kernels.hpp
+template <typename F>
+void by_dtype(int dtype, F&& f) {
+  switch (dtype) {
+    case 0: f(Tag<kF32>{}); break;
+    case 1: f(Tag<kBF16>{}); break;
+    default: f(Tag<kF16>{}); break;
+  }
+}
+
+// f(I) with a value of the per-lane index type: 32 bits whenever `work` lane
+// slots fit
+template <typename F>
+void by_width(long long work, F&& f) {
+  if (work < (1ll << 31)) {
+    f(0u);
+  } else {
+    f(0ll);
+  }
+}
+
+// f(I, Tag<MODE>) for a segments vector kernel (MODE as at SegMap)
+template <typename F>
+void by_width_mode(long long work, bool indexed, int64_t rows, F&& f) {
+  by_width(work, [&](auto i) {
+    if (!indexed) {
+      f(i, Tag<0>{});
+    } else if (rows == 1) {
+      f(i, Tag<1>{});
+    } else {
+      f(i, Tag<2>{});
+    }
+  });
 }
 
 template <int K>
 void launch_quantize_t(const void* in, void* pay, void* sc, int64_t N,
                        hipStream_t stream) {
-  constexpr int LPG = K == kF32 ? 8 : 4;
+  constexpr int LPG = kLPG<K>;
   const long long G = (N + 31) / 32;
   const long long nfull = N / 32;
   if (aligned(in, 16) && aligned(pay, 32 / LPG)) {
@@ -1128,8 +1145,8 @@ template <int K>
 void launch_dequantize_blocks_t(const u8* pay, const u8* sc, void* out,
                                 int nblocks, int64_t rows, int64_t row_elems,
                                 hipStream_t stream) {
-  constexpr int LPG = K == kF32 ? 8 : 4;
-  constexpr int EPL = 32 / LPG;
+  constexpr int LPG = kLPG<K>;
+  constexpr int EPL = kEPL<K>;
   const long long L = rows * row_elems;
   const long long Gb = (L + 31) / 32;
   // Every block's payload base is pay + r*Gb*32, so an aligned pay keeps all
@@ -1141,42 +1158,25 @@ void launch_dequantize_blocks_t(const u8* pay, const u8* sc, void* out,
     launch_dequantize_t<K>(pay, sc, out, (int64_t)nblocks * L, stream);
     return;
   }
-  // grid.y carries the block; grid.x is capped so the launch stays near the
-  // 4096 workgroups of the siblings
-  const long long xcap = 4096 / nblocks > 0 ? 4096 / nblocks : 1;
-  auto grid = [&](long long work) {
-    long long x = (work + 255) / 256;
-    if (x > xcap) x = xcap;
-    if (x < 1) x = 1;
-    return dim3((unsigned)x, (unsigned)nblocks);
-  };
   if (al && row_elems % EPL == 0) {
     const long long chunks = L / EPL;
     const long long cpr = row_elems / EPL;
-    if (chunks < (1ll << 31)) {
-      hipLaunchKernelGGL((mx8_dequantize_blocks_kernel<K, unsigned>),
-                         grid(chunks), dim3(256), 0, stream, pay, sc, out, Gb,
-                         (unsigned)chunks, (unsigned)cpr,
-                         (long long)nblocks);
-    } else {
-      hipLaunchKernelGGL((mx8_dequantize_blocks_kernel<K, long long>),
-                         grid(chunks), dim3(256), 0, stream, pay, sc, out, Gb,
-                         chunks, cpr, (long long)nblocks);
-    }
+    by_width(chunks, [&](auto i) {
+      using I = decltype(i);
+      hipLaunchKernelGGL((mx8_dequantize_blocks_kernel<K, I>),
+                         grid2d(chunks, nblocks), dim3(256), 0, stream, pay,
+                         sc, out, Gb, (I)chunks, (I)cpr, (long long)nblocks);
+    });
   } else {
     const long long slots = row_elems / EPL + 2;
     const long long total = rows * slots;
-    if (total < (1ll << 31)) {
-      hipLaunchKernelGGL((mx8_dequantize_blocks_kernel_shifted<K, unsigned>),
-                         grid(total), dim3(256), 0, stream, pay, sc, out, Gb,
-                         (long long)row_elems, (unsigned)slots,
-                         (unsigned)total, (long long)nblocks);
-    } else {
-      hipLaunchKernelGGL((mx8_dequantize_blocks_kernel_shifted<K, long long>),
-                         grid(total), dim3(256), 0, stream, pay, sc, out, Gb,
-                         (long long)row_elems, slots, total,
+    by_width(total, [&](auto i) {
+      using I = decltype(i);
+      hipLaunchKernelGGL((mx8_dequantize_blocks_kernel_shifted<K, I>),
+                         grid2d(total, nblocks), dim3(256), 0, stream, pay, sc,
+                         out, Gb, (long long)row_elems, (I)slots, (I)total,
                          (long long)nblocks);
-    }
+    });
   }
 }
 
@@ -1184,8 +1184,8 @@ template <int K>
 void launch_quantize_blocks_t(const void* in, u8* pay, u8* sc, int nblocks,
                               int64_t rows, int64_t row_elems,
                               hipStream_t stream) {
-  constexpr int LPG = K == kF32 ? 8 : 4;
-  constexpr int EPL = 32 / LPG;
+  constexpr int LPG = kLPG<K>;
+  constexpr int EPL = kEPL<K>;
   const long long L = rows * row_elems;
   const long long Gb = (L + 31) / 32;
   // Every block's payload base is pay + r*Gb*32, so an aligned pay keeps all
@@ -1198,31 +1198,21 @@ void launch_quantize_blocks_t(const void* in, u8* pay, u8* sc, int nblocks,
     launch_quantize_t<K>(in, pay, sc, (int64_t)nblocks * L, stream);
     return;
   }
-  const long long xcap = 4096 / nblocks > 0 ? 4096 / nblocks : 1;
-  auto grid = [&](long long work) {
-    long long x = (work + 255) / 256;
-    if (x > xcap) x = xcap;
-    if (x < 1) x = 1;
-    return dim3((unsigned)x, (unsigned)nblocks);
-  };
   if (al && row_elems % EPL == 0) {
     const long long chunks = L / EPL;
     const long long cpr = row_elems / EPL;
     const long long slots = Gb * LPG;
-    if (slots < (1ll << 31)) {
-      hipLaunchKernelGGL((mx8_quantize_blocks_kernel<K, unsigned>),
-                         grid(slots), dim3(256), 0, stream, in, pay, sc, Gb,
-                         (unsigned)chunks, (unsigned)cpr, (unsigned)slots,
+    by_width(slots, [&](auto i) {
+      using I = decltype(i);
+      hipLaunchKernelGGL((mx8_quantize_blocks_kernel<K, I>),
+                         grid2d(slots, nblocks), dim3(256), 0, stream, in, pay,
+                         sc, Gb, (I)chunks, (I)cpr, (I)slots,
                          (long long)nblocks);
-    } else {
-      hipLaunchKernelGGL((mx8_quantize_blocks_kernel<K, long long>),
-                         grid(slots), dim3(256), 0, stream, in, pay, sc, Gb,
-                         chunks, cpr, slots, (long long)nblocks);
-    }
+    });
   } else {
-    hipLaunchKernelGGL((mx8_quantize_blocks_kernel_scalar<K>), grid(Gb),
-                       dim3(256), 0, stream, in, pay, sc, Gb, L,
-                       (long long)row_elems, (long long)nblocks);
+    hipLaunchKernelGGL((mx8_quantize_blocks_kernel_scalar<K>),
+                       grid2d(Gb, nblocks), dim3(256), 0, stream, in, pay, sc,
+                       Gb, L, (long long)row_elems, (long long)nblocks);
   }
 }
 
@@ -1242,16 +1232,6 @@ inline SegBatch seg_batch(const Mx8SegDesc* segs, int n) {
     if (segs[k].count > b.max_count) b.max_count = segs[k].count;
   }
   return b;
-}
-
-// grid.y carries the segment; grid.x is capped so the launch stays near the
-// 4096 workgroups of the siblings
-inline dim3 seg_grid(long long work, int nsegs) {
-  const long long xcap = 4096 / nsegs > 0 ? 4096 / nsegs : 1;
-  long long x = (work + 255) / 256;
-  if (x > xcap) x = xcap;
-  if (x < 1) x = 1;
-  return dim3((unsigned)x, (unsigned)nsegs);
 }
 
 // With no index, rows == 1 and every L_p a multiple of 32, segments that
@@ -1280,45 +1260,37 @@ inline long long flat_stream_of(const Mx8SegDesc* segs, int nsegs,
   return total;
 }
 
-template <int K, typename I, int MODE>
-void launch_qseg(const void* in, const long long* idx, u8* pay, u8* sc,
-                 const SegBatch& b, long long slots, int64_t rows, int64_t S,
-                 long long cps, hipStream_t stream) {
-  hipLaunchKernelGGL((mx8_quantize_segments_kernel<K, I, MODE>),
-                     seg_grid(slots, b.n), dim3(256), 0, stream, in, idx, pay,
-                     sc, b.args, (long long)S, (I)cps, (long long)rows);
-}
-
-template <int K, typename I, int MODE>
-void launch_dseg(const u8* pay, const u8* sc, const long long* idx, void* out,
-                 const SegBatch& b, long long chunks, int64_t rows, int64_t S,
-                 long long cps, hipStream_t stream) {
-  hipLaunchKernelGGL((mx8_dequantize_segments_kernel<K, I, MODE>),
-                     seg_grid(chunks, b.n), dim3(256), 0, stream, pay, sc, idx,
-                     out, b.args, (long long)S, (I)cps, (long long)rows);
-}
-
-template <int K>
-void launch_quantize_segments_t(const void* in, const long long* idx, u8* pay,
-                                u8* sc, const Mx8SegDesc* segs, int nsegs,
-                                int64_t rows, int64_t S, int64_t after,
-                                hipStream_t stream) {
-  using T = typename Elem<K>::type;
-  constexpr int LPG = K == kF32 ? 8 : 4;
-  constexpr int EPL = 32 / LPG;
+// Both segments launchers. Q is the direction: quantizing reads the tensor
+// and writes the wire bytes, dequantizing the other way round.
+template <int K, bool Q>
+void launch_segments_t(std::conditional_t<Q, const void, void>* tensor,
+                       const long long* idx,
+                       std::conditional_t<Q, u8, const u8>* pay,
+                       std::conditional_t<Q, u8, const u8>* sc,
+                       const Mx8SegDesc* segs, int nsegs, int64_t rows,
+                       int64_t S, int64_t after, hipStream_t stream) {
+  using T = std::conditional_t<Q, const typename Elem<K>::type,
+                               typename Elem<K>::type>;
+  constexpr int LPG = kLPG<K>;
+  constexpr int EPL = kEPL<K>;
   // Every segment's payload base is pay + 32*goff, so an aligned pay keeps
-  // all of them aligned; after % EPL == 0 with an aligned in keeps every
-  // chunk's source aligned.
-  const bool al = aligned(in, 16) && aligned(pay, 32 / LPG);
+  // all of them aligned; after % EPL == 0 with an aligned tensor keeps every
+  // chunk's place in it aligned.
+  const bool al = aligned(tensor, 16) && aligned(pay, 32 / LPG);
   if (al && idx == nullptr && rows == 1) {
     int first;
     const long long total = flat_stream_of(segs, nsegs, after, &first);
     if (total == 0) return;
     if (total > 0) {
-      const T* base = reinterpret_cast<const T*>(in) + segs[first].displ * after;
+      T* base = reinterpret_cast<T*>(tensor) + segs[first].displ * after;
       if (aligned(base, 16)) {
-        launch_quantize_t<K>(base, pay + segs[first].goff * 32,
-                             sc + segs[first].goff, total, stream);
+        auto* p = pay + segs[first].goff * 32;
+        auto* s = sc + segs[first].goff;
+        if constexpr (Q) {
+          launch_quantize_t<K>(base, p, s, total, stream);
+        } else {
+          launch_dequantize_t<K>(p, s, base, total, stream);
+        }
         return;
       }
     }
@@ -1331,89 +1303,43 @@ void launch_quantize_segments_t(const void* in, const long long* idx, u8* pay,
     if (al && after % EPL == 0) {
       const long long cps = after / EPL;
       const long long chunks = rows * b.max_count * cps;
-      const long long slots = (chunks + LPG - 1) / LPG * LPG;
-      const bool small = slots < (1ll << 31);
-      if (idx == nullptr) {
-        if (small) launch_qseg<K, unsigned, 0>(in, idx, pay, sc, b, slots, rows, S, cps, stream);
-        else launch_qseg<K, long long, 0>(in, idx, pay, sc, b, slots, rows, S, cps, stream);
-      } else if (rows == 1) {
-        if (small) launch_qseg<K, unsigned, 1>(in, idx, pay, sc, b, slots, rows, S, cps, stream);
-        else launch_qseg<K, long long, 1>(in, idx, pay, sc, b, slots, rows, S, cps, stream);
-      } else {
-        if (small) launch_qseg<K, unsigned, 2>(in, idx, pay, sc, b, slots, rows, S, cps, stream);
-        else launch_qseg<K, long long, 2>(in, idx, pay, sc, b, slots, rows, S, cps, stream);
-      }
+      // lane slots of the largest segment: whole groups when quantizing
+      const long long work = Q ? (chunks + LPG - 1) / LPG * LPG : chunks;
+      by_width_mode(work, idx != nullptr, rows, [&](auto i, auto mode) {
+        using I = decltype(i);
+        constexpr int MODE = decltype(mode)::value;
+        if constexpr (Q) {
+          hipLaunchKernelGGL((mx8_quantize_segments_kernel<K, I, MODE>),
+                             grid2d(work, n), dim3(256), 0, stream, tensor,
+                             idx, pay, sc, b.args, (long long)S, (I)cps,
+                             (long long)rows);
+        } else {
+          hipLaunchKernelGGL((mx8_dequantize_segments_kernel<K, I, MODE>),
+                             grid2d(work, n), dim3(256), 0, stream, pay, sc,
+                             idx, tensor, b.args, (long long)S, (I)cps,
+                             (long long)rows);
+        }
+      });
     } else {
       const long long G = (rows * b.max_count * after + 31) / 32;
+      auto twin = [&](auto indexed) {
+        constexpr bool IDX = decltype(indexed)::value;
+        if constexpr (Q) {
+          hipLaunchKernelGGL((mx8_quantize_segments_kernel_scalar<K, IDX>),
+                             grid2d(G, n), dim3(256), 0, stream, tensor, idx,
+                             pay, sc, b.args, (long long)S, (long long)after,
+                             (long long)rows);
+        } else {
+          hipLaunchKernelGGL((mx8_dequantize_segments_kernel_scalar<K, IDX>),
+                             grid2d(G, n), dim3(256), 0, stream, pay, sc, idx,
+                             tensor, b.args, (long long)S, (long long)after,
+                             (long long)rows);
+        }
+      };
       if (idx == nullptr) {
-        hipLaunchKernelGGL((mx8_quantize_segments_kernel_scalar<K, false>),
-                           seg_grid(G, n), dim3(256), 0, stream, in, idx, pay,
-                           sc, b.args, (long long)S, (long long)after,
-                           (long long)rows);
+        twin(std::false_type{});
       } else {
-        hipLaunchKernelGGL((mx8_quantize_segments_kernel_scalar<K, true>),
-                           seg_grid(G, n), dim3(256), 0, stream, in, idx, pay,
-                           sc, b.args, (long long)S, (long long)after,
-                           (long long)rows);
-      }
-    }
-  }
-}
-
-template <int K>
-void launch_dequantize_segments_t(const u8* pay, const u8* sc,
-                                  const long long* idx, void* out,
-                                  const Mx8SegDesc* segs, int nsegs,
-                                  int64_t rows, int64_t S, int64_t after,
-                                  hipStream_t stream) {
-  using T = typename Elem<K>::type;
-  constexpr int LPG = K == kF32 ? 8 : 4;
-  constexpr int EPL = 32 / LPG;
-  const bool al = aligned(out, 16) && aligned(pay, 32 / LPG);
-  if (al && idx == nullptr && rows == 1) {
-    int first;
-    const long long total = flat_stream_of(segs, nsegs, after, &first);
-    if (total == 0) return;
-    if (total > 0) {
-      T* base = reinterpret_cast<T*>(out) + segs[first].displ * after;
-      if (aligned(base, 16)) {
-        launch_dequantize_t<K>(pay + segs[first].goff * 32,
-                               sc + segs[first].goff, base, total, stream);
-        return;
-      }
-    }
-  }
-  for (int s0 = 0; s0 < nsegs; s0 += kMaxMx8SegsPerLaunch) {
-    const int n = nsegs - s0 < kMaxMx8SegsPerLaunch ? nsegs - s0
-                                                    : kMaxMx8SegsPerLaunch;
-    const SegBatch b = seg_batch(segs + s0, n);
-    if (b.max_count == 0) continue;
-    if (al && after % EPL == 0) {
-      const long long cps = after / EPL;
-      const long long chunks = rows * b.max_count * cps;
-      const bool small = chunks < (1ll << 31);
-      if (idx == nullptr) {
-        if (small) launch_dseg<K, unsigned, 0>(pay, sc, idx, out, b, chunks, rows, S, cps, stream);
-        else launch_dseg<K, long long, 0>(pay, sc, idx, out, b, chunks, rows, S, cps, stream);
-      } else if (rows == 1) {
-        if (small) launch_dseg<K, unsigned, 1>(pay, sc, idx, out, b, chunks, rows, S, cps, stream);
-        else launch_dseg<K, long long, 1>(pay, sc, idx, out, b, chunks, rows, S, cps, stream);
-      } else {
-        if (small) launch_dseg<K, unsigned, 2>(pay, sc, idx, out, b, chunks, rows, S, cps, stream);
-        else launch_dseg<K, long long, 2>(pay, sc, idx, out, b, chunks, rows, S, cps, stream);
-      }
-    } else {
-      const long long G = (rows * b.max_count * after + 31) / 32;
-      if (idx == nullptr) {
-        hipLaunchKernelGGL((mx8_dequantize_segments_kernel_scalar<K, false>),
-                           seg_grid(G, n), dim3(256), 0, stream, pay, sc, idx,
-                           out, b.args, (long long)S, (long long)after,
-                           (long long)rows);
-      } else {
-        hipLaunchKernelGGL((mx8_dequantize_segments_kernel_scalar<K, true>),
-                           seg_grid(G, n), dim3(256), 0, stream, pay, sc, idx,
-                           out, b.args, (long long)S, (long long)after,
-                           (long long)rows);
+        twin(std::true_type{});
       }
     }
   }
@@ -1427,14 +1353,12 @@ void launch_mx8_quantize_segments(const void* in, const int64_t* idx,
                                   int64_t rows, int64_t S, int64_t after,
                                   int dtype, hipStream_t stream) {
   if (nsegs <= 0 || rows <= 0 || S <= 0 || after <= 0) return;
-  const long long* ix = reinterpret_cast<const long long*>(idx);
-  u8* pay = static_cast<u8*>(payload);
-  u8* sc = static_cast<u8*>(scales);
-  switch (dtype) {
-    case 0: launch_quantize_segments_t<kF32>(in, ix, pay, sc, segs, nsegs, rows, S, after, stream); break;
-    case 1: launch_quantize_segments_t<kBF16>(in, ix, pay, sc, segs, nsegs, rows, S, after, stream); break;
-    default: launch_quantize_segments_t<kF16>(in, ix, pay, sc, segs, nsegs, rows, S, after, stream); break;
-  }
+  by_dtype(dtype, [&](auto k) {
+    launch_segments_t<k, true>(in, reinterpret_cast<const long long*>(idx),
+                               static_cast<u8*>(payload),
+                               static_cast<u8*>(scales), segs, nsegs, rows, S,
+                               after, stream);
+  });
 }
 
 void launch_mx8_dequantize_segments(const void* payload, const void* scales,
@@ -1443,27 +1367,23 @@ void launch_mx8_dequantize_segments(const void* payload, const void* scales,
                                     int64_t rows, int64_t S, int64_t after,
                                     int dtype, hipStream_t stream) {
   if (nsegs <= 0 || rows <= 0 || S <= 0 || after <= 0) return;
-  const long long* ix = reinterpret_cast<const long long*>(idx);
-  const u8* pay = static_cast<const u8*>(payload);
-  const u8* sc = static_cast<const u8*>(scales);
-  switch (dtype) {
-    case 0: launch_dequantize_segments_t<kF32>(pay, sc, ix, out, segs, nsegs, rows, S, after, stream); break;
-    case 1: launch_dequantize_segments_t<kBF16>(pay, sc, ix, out, segs, nsegs, rows, S, after, stream); break;
-    default: launch_dequantize_segments_t<kF16>(pay, sc, ix, out, segs, nsegs, rows, S, after, stream); break;
-  }
+  by_dtype(dtype, [&](auto k) {
+    launch_segments_t<k, false>(out, reinterpret_cast<const long long*>(idx),
+                                static_cast<const u8*>(payload),
+                                static_cast<const u8*>(scales), segs, nsegs,
+                                rows, S, after, stream);
+  });
 }
 
 void launch_mx8_quantize_blocks(const void* in, void* payload, void* scales,
                                 int nblocks, int64_t rows, int64_t row_elems,
                                 int dtype, hipStream_t stream) {
   if (nblocks <= 0 || rows <= 0 || row_elems <= 0) return;
-  u8* pay = static_cast<u8*>(payload);
-  u8* sc = static_cast<u8*>(scales);
-  switch (dtype) {
-    case 0: launch_quantize_blocks_t<kF32>(in, pay, sc, nblocks, rows, row_elems, stream); break;
-    case 1: launch_quantize_blocks_t<kBF16>(in, pay, sc, nblocks, rows, row_elems, stream); break;
-    default: launch_quantize_blocks_t<kF16>(in, pay, sc, nblocks, rows, row_elems, stream); break;
-  }
+  by_dtype(dtype, [&](auto k) {
+    launch_quantize_blocks_t<k>(in, static_cast<u8*>(payload),
+                                static_cast<u8*>(scales), nblocks, rows,
+                                row_elems, stream);
+  });
 }
 
 void launch_mx8_dequantize_blocks(const void* payload, const void* scales,
@@ -1471,36 +1391,30 @@ void launch_mx8_dequantize_blocks(const void* payload, const void* scales,
                                   int64_t row_elems, int dtype,
                                   hipStream_t stream) {
   if (nblocks <= 0 || rows <= 0 || row_elems <= 0) return;
-  const u8* pay = static_cast<const u8*>(payload);
-  const u8* sc = static_cast<const u8*>(scales);
-  switch (dtype) {
-    case 0: launch_dequantize_blocks_t<kF32>(pay, sc, out, nblocks, rows, row_elems, stream); break;
-    case 1: launch_dequantize_blocks_t<kBF16>(pay, sc, out, nblocks, rows, row_elems, stream); break;
-    default: launch_dequantize_blocks_t<kF16>(pay, sc, out, nblocks, rows, row_elems, stream); break;
-  }
+  by_dtype(dtype, [&](auto k) {
+    launch_dequantize_blocks_t<k>(static_cast<const u8*>(payload),
+                                  static_cast<const u8*>(scales), out, nblocks,
+                                  rows, row_elems, stream);
+  });
 }
 
 void launch_mx8_reduce_to(const void* payload_in, const void* scales_in,
                           void* out, int64_t n_elems, int nranks, int dtype,
                           hipStream_t stream) {
   if (n_elems <= 0) return;
-  const u8* pin = static_cast<const u8*>(payload_in);
-  const u8* sin = static_cast<const u8*>(scales_in);
-  switch (dtype) {
-    case 0: launch_reduce_to_t<kF32>(pin, sin, out, n_elems, nranks, stream); break;
-    case 1: launch_reduce_to_t<kBF16>(pin, sin, out, n_elems, nranks, stream); break;
-    default: launch_reduce_to_t<kF16>(pin, sin, out, n_elems, nranks, stream); break;
-  }
+  by_dtype(dtype, [&](auto k) {
+    launch_reduce_to_t<k>(static_cast<const u8*>(payload_in),
+                          static_cast<const u8*>(scales_in), out, n_elems,
+                          nranks, stream);
+  });
 }
 
 void launch_mx8_quantize(const void* in, void* payload, void* scales,
                          int64_t n_elems, int dtype, hipStream_t stream) {
   if (n_elems <= 0) return;
-  switch (dtype) {
-    case 0: launch_quantize_t<kF32>(in, payload, scales, n_elems, stream); break;
-    case 1: launch_quantize_t<kBF16>(in, payload, scales, n_elems, stream); break;
-    default: launch_quantize_t<kF16>(in, payload, scales, n_elems, stream); break;
-  }
+  by_dtype(dtype, [&](auto k) {
+    launch_quantize_t<k>(in, payload, scales, n_elems, stream);
+  });
 }
 
 void launch_mx8_reduce(const void* payload_in, const void* scales_in,
@@ -1525,11 +1439,9 @@ void launch_mx8_reduce(const void* payload_in, const void* scales_in,
 void launch_mx8_dequantize(const void* payload, const void* scales, void* out,
                            int64_t n_elems, int dtype, hipStream_t stream) {
   if (n_elems <= 0) return;
-  switch (dtype) {
-    case 0: launch_dequantize_t<kF32>(payload, scales, out, n_elems, stream); break;
-    case 1: launch_dequantize_t<kBF16>(payload, scales, out, n_elems, stream); break;
-    default: launch_dequantize_t<kF16>(payload, scales, out, n_elems, stream); break;
-  }
+  by_dtype(dtype, [&](auto k) {
+    launch_dequantize_t<k>(payload, scales, out, n_elems, stream);
+  });
 }
 
 } // namespace m4a

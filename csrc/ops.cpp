@@ -882,26 +882,37 @@ Tensor mx8_dequantize_groups(const Tensor& pay, const Tensor& sc) {
                    d);
 }
 
-int mx8_dtype_code(at::ScalarType t) {
+// The dtype code of kernels.hpp; `who` names the caller in the message.
+int mx8_dtype_code(at::ScalarType t, const char* who = "mxfp8 compression") {
   switch (t) {
     case at::kFloat: return 0;
     case at::kBFloat16: return 1;
     case at::kHalf: return 2;
     default:
-      TORCH_CHECK(false, "mpi4torch_amd: mxfp8 compression supports "
-                  "float32, bfloat16 and float16 tensors, got ", t);
+      TORCH_CHECK(false, "mpi4torch_amd: ", who, " supports float32, "
+                  "bfloat16 and float16 tensors, got ", t);
   }
 }
 
+// The codec functions below take optional outputs: a caller's contiguous
+// buffer of the result's shape (or longer, where noted) is written in place
+// and returned; without one the result is allocated.
+Tensor out_or_empty(const c10::optional<Tensor>& out, at::IntArrayRef sizes,
+                    const at::TensorOptions& opts) {
+  return out.has_value() ? *out : at::empty(sizes, opts);
+}
+
 // flat contiguous x -> (payload [G*32] u8, scales [G] u8), G = ceil(N/32)
-std::pair<Tensor, Tensor> mx8_quantize(const Tensor& x) {
+std::pair<Tensor, Tensor> mx8_quantize(
+    const Tensor& x, const c10::optional<Tensor>& payload_out = c10::nullopt,
+    const c10::optional<Tensor>& scales_out = c10::nullopt) {
   const int dt = mx8_dtype_code(x.scalar_type());
   const int64_t N = x.numel();
   const int64_t G = (N + 31) / 32;
   auto bopts = x.options().dtype(at::kByte);
+  auto pay = out_or_empty(payload_out, {G * 32}, bopts);
+  auto sc = out_or_empty(scales_out, {G}, bopts);
   if (x.is_cuda()) {
-    auto pay = at::empty({G * 32}, bopts);
-    auto sc = at::empty({G}, bopts);
     launch_mx8_quantize(x.data_ptr(), pay.data_ptr(), sc.data_ptr(), N, dt,
                         current_gpu_stream(x));
     return {pay, sc};
@@ -909,7 +920,22 @@ std::pair<Tensor, Tensor> mx8_quantize(const Tensor& x) {
   auto padded = at::zeros({G * 32}, x.options().dtype(at::kFloat));
   padded.narrow(0, 0, N).copy_(x.view({-1}));
   auto ps = mx8_quantize_groups(padded.view({G, 32}));
-  return {ps.first.view({-1}), ps.second};
+  if (!payload_out.has_value()) return {ps.first.view({-1}), ps.second};
+  pay.copy_(ps.first.view({-1}));
+  sc.copy_(ps.second);
+  return {pay, sc};
+}
+
+// The CPU composites' sum: P copies, pin [P * n*32], sin [P * n] -> [n, 32]
+// fp32, ((d_0 + d_1) + ...) in rank order on dequantized values.
+Tensor mx8_sum_copies(const Tensor& pin, const Tensor& sin, int64_t n, int P) {
+  auto pv = pin.view({P, n, 32});
+  auto sv = sin.view({P, n});
+  auto acc = mx8_dequantize_groups(pv[0], sv[0]);
+  for (int r = 1; r < P; ++r) {
+    acc = acc + mx8_dequantize_groups(pv[r], sv[r]);
+  }
+  return acc;
 }
 
 // P copies: pin [P * n*32], sin [P * n] -> pout [n*32], sout [n] (views ok)
@@ -921,30 +947,26 @@ void mx8_reduce(const Tensor& pin, const Tensor& sin, Tensor& pout,
                       sout.data_ptr(), n, P, current_gpu_stream(pin));
     return;
   }
-  auto pv = pin.view({P, n, 32});
-  auto sv = sin.view({P, n});
-  auto acc = mx8_dequantize_groups(pv[0], sv[0]);
-  for (int r = 1; r < P; ++r) {
-    acc = acc + mx8_dequantize_groups(pv[r], sv[r]);
-  }
-  auto ps = mx8_quantize_groups(acc);
+  auto ps = mx8_quantize_groups(mx8_sum_copies(pin, sin, n, P));
   pout.copy_(ps.first.view({-1}));
   sout.copy_(ps.second);
 }
 
 // payload [G*32], scales [G] -> flat [numel] of `dtype`
 Tensor mx8_dequantize(const Tensor& pay, const Tensor& sc, int64_t numel,
-                      at::ScalarType dtype) {
+                      at::ScalarType dtype,
+                      const c10::optional<Tensor>& out_opt = c10::nullopt) {
   const int dt = mx8_dtype_code(dtype);
   if (pay.is_cuda()) {
-    auto out = at::empty({numel}, pay.options().dtype(dtype));
+    auto out = out_or_empty(out_opt, {numel}, pay.options().dtype(dtype));
     launch_mx8_dequantize(pay.data_ptr(), sc.data_ptr(), out.data_ptr(),
                           numel, dt, current_gpu_stream(pay));
     return out;
   }
   const int64_t G = sc.numel();
   auto d = mx8_dequantize_groups(pay.view({G, 32}), sc).view({-1});
-  return d.narrow(0, 0, numel).to(dtype);
+  auto res = d.narrow(0, 0, numel).to(dtype);
+  return out_opt.has_value() ? out_opt->copy_(res) : res;
 }
 
 // P copies: pin [P * G*32], sin [P * G], G = ceil(numel/32) -> flat [numel]
@@ -952,22 +974,58 @@ Tensor mx8_dequantize(const Tensor& pay, const Tensor& sc, int64_t numel,
 // rank-order sum of the dequantized copies, then .to(dtype) — no
 // requantization. A 255 scale in any copy makes that group NaN.
 Tensor mx8_reduce_to(const Tensor& pin, const Tensor& sin, int64_t numel,
-                     int P, at::ScalarType dtype) {
+                     int P, at::ScalarType dtype,
+                     const c10::optional<Tensor>& out_opt = c10::nullopt) {
   const int dt = mx8_dtype_code(dtype);
   if (pin.is_cuda()) {
-    auto out = at::empty({numel}, pin.options().dtype(dtype));
+    auto out = out_or_empty(out_opt, {numel}, pin.options().dtype(dtype));
     launch_mx8_reduce_to(pin.data_ptr(), sin.data_ptr(), out.data_ptr(),
                          numel, P, dt, current_gpu_stream(pin));
     return out;
   }
-  const int64_t G = (numel + 31) / 32;
-  auto pv = pin.view({P, G, 32});
-  auto sv = sin.view({P, G});
-  auto acc = mx8_dequantize_groups(pv[0], sv[0]);
-  for (int r = 1; r < P; ++r) {
-    acc = acc + mx8_dequantize_groups(pv[r], sv[r]);
-  }
-  return acc.view({-1}).narrow(0, 0, numel).to(dtype);
+  auto acc = mx8_sum_copies(pin, sin, (numel + 31) / 32, P);
+  auto res = acc.view({-1}).narrow(0, 0, numel).to(dtype);
+  return out_opt.has_value() ? out_opt->copy_(res) : res;
+}
+
+// One grouped Transport::exchange of quantized groups. On either side peer
+// p's piece is the groups [off[p], off[p] + cnt[p]) of (pay, sc): sent from
+// there, or received into them. Payload and scales travel as two contiguous
+// pieces per peer. Empty pieces are not listed: both transports skip them on
+// both ends of a pair anyway.
+struct Mx8Side {
+  Tensor pay, sc;
+  std::vector<int64_t> off, cnt;  // per peer, in groups
+};
+
+void mx8_exchange(Transport& tr, const Mx8Side& send, const Mx8Side& recv) {
+  std::vector<Tensor> sends, recvs;
+  std::vector<int> speers, rpeers;
+  auto list = [](const Mx8Side& s, std::vector<Tensor>& bufs,
+                 std::vector<int>& peers) {
+    for (int p = 0; p < (int)s.cnt.size(); ++p) {
+      if (s.cnt[p] == 0) continue;
+      bufs.push_back(s.pay.narrow(0, s.off[p] * 32, s.cnt[p] * 32));
+      bufs.push_back(s.sc.narrow(0, s.off[p], s.cnt[p]));
+      peers.insert(peers.end(), 2, p);
+    }
+  };
+  list(send, sends, speers);
+  list(recv, recvs, rpeers);
+  tr.exchange(sends, speers, recvs, rpeers);
+}
+
+// Equal blocks of Gb groups, block p for peer p: the exchange of
+// mx8_reducescatter and mx8_alltoall. Returns the P received blocks.
+std::pair<Tensor, Tensor> mx8_exchange_blocks(Transport& tr, const Tensor& pay,
+                                              const Tensor& sc, int64_t Gb) {
+  const int P = tr.size();
+  auto stg_pay = at::empty({(int64_t)P * Gb * 32}, pay.options());
+  auto stg_sc = at::empty({(int64_t)P * Gb}, sc.options());
+  std::vector<int64_t> off(P), cnt(P, Gb);
+  for (int p = 0; p < P; ++p) off[p] = (int64_t)p * Gb;
+  mx8_exchange(tr, {pay, sc, off, cnt}, {stg_pay, stg_sc, off, cnt});
+  return {stg_pay, stg_sc};
 }
 
 // The reduce-scatter sibling of mx8_allreduce, phases 1-2 only: `packed` is
@@ -994,34 +1052,13 @@ Tensor mx8_reducescatter(Transport& tr, const Tensor& packed, int64_t L) {
     pay = at::empty({(int64_t)P * Gb * 32}, bopts);
     sc = at::empty({(int64_t)P * Gb}, bopts);
     for (int p = 0; p < P; ++p) {
-      auto blk = packed.narrow(0, (int64_t)p * L, L);
-      if (packed.is_cuda()) {
-        launch_mx8_quantize(blk.data_ptr(),
-                            pay.narrow(0, (int64_t)p * Gb * 32, Gb * 32)
-                                .data_ptr(),
-                            sc.narrow(0, (int64_t)p * Gb, Gb).data_ptr(), L,
-                            mx8_dtype_code(packed.scalar_type()),
-                            current_gpu_stream(packed));
-      } else {
-        auto q = mx8_quantize(blk);
-        pay.narrow(0, (int64_t)p * Gb * 32, Gb * 32).copy_(q.first);
-        sc.narrow(0, (int64_t)p * Gb, Gb).copy_(q.second);
-      }
+      mx8_quantize(packed.narrow(0, (int64_t)p * L, L),
+                   pay.narrow(0, (int64_t)p * Gb * 32, Gb * 32),
+                   sc.narrow(0, (int64_t)p * Gb, Gb));
     }
   }
-  auto stg_pay = at::empty({(int64_t)P * Gb * 32}, bopts);
-  auto stg_sc = at::empty({(int64_t)P * Gb}, bopts);
-  std::vector<Tensor> sends(2 * P), recvs(2 * P);
-  std::vector<int> peers(2 * P);
-  for (int p = 0; p < P; ++p) {
-    sends[2 * p] = pay.narrow(0, (int64_t)p * Gb * 32, Gb * 32);
-    sends[2 * p + 1] = sc.narrow(0, (int64_t)p * Gb, Gb);
-    recvs[2 * p] = stg_pay.narrow(0, (int64_t)p * Gb * 32, Gb * 32);
-    recvs[2 * p + 1] = stg_sc.narrow(0, (int64_t)p * Gb, Gb);
-    peers[2 * p] = peers[2 * p + 1] = p;
-  }
-  tr.exchange(sends, peers, recvs, peers);
-  return mx8_reduce_to(stg_pay, stg_sc, L, P, packed.scalar_type());
+  auto stg = mx8_exchange_blocks(tr, pay, sc, Gb);
+  return mx8_reduce_to(stg.first, stg.second, L, P, packed.scalar_type());
 }
 
 // P gathered blocks: pay [P * Gb*32], sc [P * Gb], Gb = ceil(L/32),
@@ -1031,13 +1068,15 @@ Tensor mx8_reducescatter(Transport& tr, const Tensor& packed, int64_t L) {
 // A 255 scale gives a NaN group in that block only.
 Tensor mx8_dequantize_blocks(const Tensor& pay, const Tensor& sc, int P,
                              int64_t rows, int64_t row_elems,
-                             at::ScalarType dtype) {
+                             at::ScalarType dtype,
+                             const c10::optional<Tensor>& out_opt =
+                                 c10::nullopt) {
   const int dt = mx8_dtype_code(dtype);
   TORCH_CHECK(P >= 1 && P <= 65535,
               "mpi4torch_amd: mx8_dequantize_blocks supports 1..65535 "
               "blocks, got ", P);
-  auto out = at::empty({rows, (int64_t)P, row_elems},
-                       pay.options().dtype(dtype));
+  auto out = out_or_empty(out_opt, {rows, (int64_t)P, row_elems},
+                          pay.options().dtype(dtype));
   if (out.numel() == 0) return out;
   if (pay.is_cuda()) {
     launch_mx8_dequantize_blocks(pay.data_ptr(), sc.data_ptr(),
@@ -1085,17 +1124,18 @@ Tensor mx8_allgather(Transport& tr, const Tensor& in, int64_t rows,
 // The all-to-all head, normative here: block p is mx8_quantize of the
 // contiguous copy of in[:, p, :], so its groups start at the block and its
 // partial last group is zero-padded.
-std::pair<Tensor, Tensor> mx8_quantize_blocks(const Tensor& in, int P,
-                                              int64_t rows,
-                                              int64_t row_elems) {
+std::pair<Tensor, Tensor> mx8_quantize_blocks(
+    const Tensor& in, int P, int64_t rows, int64_t row_elems,
+    const c10::optional<Tensor>& payload_out = c10::nullopt,
+    const c10::optional<Tensor>& scales_out = c10::nullopt) {
   const int dt = mx8_dtype_code(in.scalar_type());
   TORCH_CHECK(P >= 1 && P <= 65535,
               "mpi4torch_amd: mx8_quantize_blocks supports 1..65535 "
               "blocks, got ", P);
   const int64_t Gb = (rows * row_elems + 31) / 32;
   auto bopts = in.options().dtype(at::kByte);
-  auto pay = at::empty({(int64_t)P, Gb * 32}, bopts);
-  auto sc = at::empty({(int64_t)P, Gb}, bopts);
+  auto pay = out_or_empty(payload_out, {(int64_t)P, Gb * 32}, bopts);
+  auto sc = out_or_empty(scales_out, {(int64_t)P, Gb}, bopts);
   if (pay.numel() == 0) return {pay, sc};
   if (in.is_cuda()) {
     launch_mx8_quantize_blocks(in.data_ptr(), pay.data_ptr(), sc.data_ptr(),
@@ -1128,22 +1168,9 @@ Tensor mx8_alltoall(Transport& tr, const Tensor& in, int64_t rows_s,
   const int P = tr.size();
   const int64_t Gb = (rows_s * row_s + 31) / 32;
   auto q = mx8_quantize_blocks(in, P, rows_s, row_s);
-  auto pay = q.first.view({-1});
-  auto sc = q.second.view({-1});
-  auto bopts = in.options().dtype(at::kByte);
-  auto stg_pay = at::empty({(int64_t)P * Gb * 32}, bopts);
-  auto stg_sc = at::empty({(int64_t)P * Gb}, bopts);
-  std::vector<Tensor> sends(2 * P), recvs(2 * P);
-  std::vector<int> peers(2 * P);
-  for (int p = 0; p < P; ++p) {
-    sends[2 * p] = pay.narrow(0, (int64_t)p * Gb * 32, Gb * 32);
-    sends[2 * p + 1] = sc.narrow(0, (int64_t)p * Gb, Gb);
-    recvs[2 * p] = stg_pay.narrow(0, (int64_t)p * Gb * 32, Gb * 32);
-    recvs[2 * p + 1] = stg_sc.narrow(0, (int64_t)p * Gb, Gb);
-    peers[2 * p] = peers[2 * p + 1] = p;
-  }
-  tr.exchange(sends, peers, recvs, peers);
-  return mx8_dequantize_blocks(stg_pay, stg_sc, P, rows_g, row_g,
+  auto stg = mx8_exchange_blocks(tr, q.first.view({-1}), q.second.view({-1}),
+                                 Gb);
+  return mx8_dequantize_blocks(stg.first, stg.second, P, rows_g, row_g,
                                in.scalar_type());
 }
 
@@ -1155,6 +1182,11 @@ struct Mx8SegPlan {
   std::vector<int64_t> groups;  // G_p
   int64_t slices = 0;           // sum of counts
   int64_t total_groups = 0;     // sum of G_p
+  std::vector<int64_t> goffs() const {
+    std::vector<int64_t> o;
+    for (const auto& s : segs) o.push_back(s.goff);
+    return o;
+  }
 };
 
 Mx8SegPlan mx8_seg_plan(const std::vector<int64_t>& counts, int64_t rows,
@@ -1280,32 +1312,14 @@ Tensor mx8_alltoall_pairwise(Transport& tr, const Tensor& in, int64_t rows,
                              const std::vector<int64_t>& recv_counts,
                              const c10::optional<Tensor>& send_order,
                              const c10::optional<Tensor>& recv_order) {
-  const int P = tr.size();
   const auto sp = mx8_seg_plan(send_counts, rows, after);
   const auto rp = mx8_seg_plan(recv_counts, rows, after);
   auto q = mx8_quantize_segments(in, rows, after, send_counts, send_order);
   auto bopts = in.options().dtype(at::kByte);
   auto stg_pay = at::empty({rp.total_groups * 32}, bopts);
   auto stg_sc = at::empty({rp.total_groups}, bopts);
-  std::vector<Tensor> sends, recvs;
-  std::vector<int> speers, rpeers;
-  for (int p = 0; p < P; ++p) {
-    if (sp.groups[p] > 0) {
-      sends.push_back(
-          q.first.narrow(0, sp.segs[p].goff * 32, sp.groups[p] * 32));
-      sends.push_back(q.second.narrow(0, sp.segs[p].goff, sp.groups[p]));
-      speers.push_back(p);
-      speers.push_back(p);
-    }
-    if (rp.groups[p] > 0) {
-      recvs.push_back(
-          stg_pay.narrow(0, rp.segs[p].goff * 32, rp.groups[p] * 32));
-      recvs.push_back(stg_sc.narrow(0, rp.segs[p].goff, rp.groups[p]));
-      rpeers.push_back(p);
-      rpeers.push_back(p);
-    }
-  }
-  tr.exchange(sends, speers, recvs, rpeers);
+  mx8_exchange(tr, {q.first, q.second, sp.goffs(), sp.groups},
+               {stg_pay, stg_sc, rp.goffs(), rp.groups});
   return mx8_dequantize_segments(stg_pay, stg_sc, rows, after, recv_counts,
                                  recv_order, in.scalar_type());
 }
@@ -1335,16 +1349,10 @@ Tensor mx8_allreduce(Transport& tr, const Tensor& in) {
   auto bopts = in.options().dtype(at::kByte);
   auto stg_pay = at::empty({(int64_t)P * cm * 32}, bopts);
   auto stg_sc = at::empty({(int64_t)P * cm}, bopts);
-  std::vector<Tensor> sends(2 * P), recvs(2 * P);
-  std::vector<int> peers(2 * P);
-  for (int p = 0; p < P; ++p) {
-    sends[2 * p] = nz_narrow(q.first, displs[p] * 32, counts[p] * 32);
-    sends[2 * p + 1] = nz_narrow(q.second, displs[p], counts[p]);
-    recvs[2 * p] = nz_narrow(stg_pay, (int64_t)p * cm * 32, cm * 32);
-    recvs[2 * p + 1] = nz_narrow(stg_sc, (int64_t)p * cm, cm);
-    peers[2 * p] = peers[2 * p + 1] = p;
-  }
-  tr.exchange(sends, peers, recvs, peers);
+  std::vector<int64_t> stg_off(P), stg_cnt(P, cm);
+  for (int p = 0; p < P; ++p) stg_off[p] = (int64_t)p * cm;
+  mx8_exchange(tr, {q.first, q.second, displs, counts},
+               {stg_pay, stg_sc, stg_off, stg_cnt});
   // phase 2: fused reduce of the P copies of the owned groups
   auto out_pay = at::empty({G * 32}, bopts);
   auto out_sc = at::empty({G}, bopts);
@@ -1357,24 +1365,12 @@ Tensor mx8_allreduce(Transport& tr, const Tensor& in) {
     tr.allgather_equal(my_pay, out_pay);
     tr.allgather_equal(my_sc, out_sc);
   } else {
-    std::vector<Tensor> s2, r2;
-    std::vector<int> sp, rp;
-    for (int p = 0; p < P; ++p) {
-      if (p == me) continue;
-      if (cm > 0) {
-        s2.push_back(my_pay);
-        sp.push_back(p);
-        s2.push_back(my_sc);
-        sp.push_back(p);
-      }
-      if (counts[p] > 0) {
-        r2.push_back(out_pay.narrow(0, displs[p] * 32, counts[p] * 32));
-        rp.push_back(p);
-        r2.push_back(out_sc.narrow(0, displs[p], counts[p]));
-        rp.push_back(p);
-      }
-    }
-    tr.exchange(s2, sp, r2, rp);
+    // the owned block to every other rank, every other rank's block back
+    std::vector<int64_t> own_off(P, displs[me]), own_cnt(P, cm);
+    auto their_cnt = counts;
+    own_cnt[me] = their_cnt[me] = 0;
+    mx8_exchange(tr, {out_pay, out_sc, own_off, own_cnt},
+                 {out_pay, out_sc, displs, their_cnt});
   }
   return mx8_dequantize(out_pay, out_sc, N, in.scalar_type())
       .view(in.sizes());
@@ -1433,6 +1429,42 @@ void poison_inplace_input(const Tensor& input) {
     auto& input_nc = const_cast<Tensor&>(input);
     torch::autograd::set_history(input_nc, node);
   }
+}
+
+// The frame of a collective front-end. With an input that requires grad,
+// make_grad_fn(comm) builds the backward node and its next edges are set
+// here; body(tr, in, stager) runs below autograd on the staged contiguous
+// input and returns the result still on the transport's side; the frame
+// brings it back and attaches history.
+template <typename MakeNode, typename Body>
+Tensor collective_frame(Communicator& comm, const Tensor& input,
+                        MakeNode&& make_grad_fn, Body&& body) {
+  std::shared_ptr<Node> grad_fn;
+  if (torch::autograd::compute_requires_grad(input)) {
+    grad_fn = make_grad_fn(
+        c10::intrusive_ptr<Communicator>::unsafe_reclaim_from_nonowning(&comm));
+    grad_fn->set_next_edges(torch::autograd::collect_next_edges(input));
+  }
+  auto result = [&]() {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    DeviceStager stager(input);
+    auto in = stager.to_comm(input).contiguous().variable_data();
+    return stager.from_comm(body(comm.tr_for(in), in, stager));
+  }();
+  attach_history(result, grad_fn);
+  return result;
+}
+
+// The compressed collectives' input check; opname is the front-end's.
+void check_mx8_input(const char* opname, const Tensor& t) {
+  (void)mx8_dtype_code(t.scalar_type(), opname);
+}
+
+// World of one: nothing crosses a wire, so nothing is compressed and the
+// result is an exact clone. force_full_path on a GPU runs the whole pipeline
+// instead: the codec kernels around a self-exchange.
+bool world1_shortcut(const Transport& tr, const Tensor& in) {
+  return tr.size() == 1 && !(config().force_full_path && in.is_cuda());
 }
 
 } // namespace
@@ -1511,34 +1543,17 @@ Tensor Communicator::AllreduceCompressed(const Tensor& input, int64_t op) {
   TORCH_CHECK(op == kSum,
               "mpi4torch_amd: AllreduceCompressed supports MPI_SUM only "
               "(got ", red_op_name(op), ")");
-  TORCH_CHECK(input.scalar_type() == at::kFloat ||
-                  input.scalar_type() == at::kBFloat16 ||
-                  input.scalar_type() == at::kHalf,
-              "mpi4torch_amd: AllreduceCompressed supports float32, "
-              "bfloat16 and float16 tensors, got ", input.scalar_type());
-  std::shared_ptr<M4ANode> grad_fn;
-  if (torch::autograd::compute_requires_grad(input)) {
-    grad_fn = make_node<AllreduceCompressedBackward>(
-        c10::intrusive_ptr<Communicator>::unsafe_reclaim_from_nonowning(this));
-    grad_fn->set_next_edges(torch::autograd::collect_next_edges(input));
-  }
-  auto result = [&]() {
-    at::AutoDispatchBelowADInplaceOrView guard;
-    DeviceStager stager(input);
-    auto in = stager.to_comm(input).contiguous().variable_data();
-    auto& tr = tr_for(in);
-    debug_check_collective(group_name_, "AllreduceCompressed", in, {op});
-    if (in.numel() == 0) return stager.from_comm(in.clone());
-    // World of one: nothing crosses a wire, so nothing is compressed — the
-    // result is an exact clone. force_full_path (GPU) runs the whole
-    // pipeline instead: self-exchange, all three kernels, allgather.
-    if (tr.size() == 1 && !(config().force_full_path && in.is_cuda())) {
-      return stager.from_comm(fast_clone(in));
-    }
-    return stager.from_comm(mx8_allreduce(tr, in));
-  }();
-  attach_history(result, grad_fn);
-  return result;
+  check_mx8_input("AllreduceCompressed", input);
+  return collective_frame(
+      *this, input,
+      [](auto comm) { return make_node<AllreduceCompressedBackward>(comm); },
+      [&](Transport& tr, const Tensor& in, const DeviceStager&) {
+        debug_check_collective(group_name_, "AllreduceCompressed", in, {op});
+        if (in.numel() == 0) return in.clone();
+        // full path: self-exchange, all three kernels, allgather
+        if (world1_shortcut(tr, in)) return fast_clone(in);
+        return mx8_allreduce(tr, in);
+      });
 }
 
 // ---------------------------------------------------------------------------
@@ -2227,24 +2242,13 @@ struct ReducescatterCompressedBackward : public M4ANode {
 
 Tensor Communicator::ReducescatterCompressed(const Tensor& input,
                                              int64_t axis) {
-  TORCH_CHECK(input.scalar_type() == at::kFloat ||
-                  input.scalar_type() == at::kBFloat16 ||
-                  input.scalar_type() == at::kHalf,
-              "mpi4torch_amd: ReducescatterCompressed supports float32, "
-              "bfloat16 and float16 tensors, got ", input.scalar_type());
+  check_mx8_input("ReducescatterCompressed", input);
   axis = at::maybe_wrap_dim(axis, input.dim());
-  std::shared_ptr<M4ANode> grad_fn;
-  if (torch::autograd::compute_requires_grad(input)) {
-    grad_fn = make_node<ReducescatterCompressedBackward>(
-        c10::intrusive_ptr<Communicator>::unsafe_reclaim_from_nonowning(this),
-        axis);
-    grad_fn->set_next_edges(torch::autograd::collect_next_edges(input));
-  }
-  auto result = [&]() {
-    at::AutoDispatchBelowADInplaceOrView guard;
-    DeviceStager stager(input);
-    auto in = stager.to_comm(input).contiguous().variable_data();
-    auto& tr = tr_for(in);
+  auto make_grad_fn = [&](auto comm) {
+    return make_node<ReducescatterCompressedBackward>(comm, axis);
+  };
+  auto body = [&](Transport& tr, const Tensor& in,
+                  const DeviceStager&) -> Tensor {
     const int P = tr.size();
     TORCH_CHECK(in.size(axis) % P == 0,
                 "mpi4torch_amd: ReducescatterCompressed requires equal "
@@ -2254,15 +2258,9 @@ Tensor Communicator::ReducescatterCompressed(const Tensor& input,
     debug_check_collective(group_name_, "ReducescatterCompressed", in, {axis});
     auto outsizes = in.sizes().vec();
     outsizes[axis] = in.size(axis) / P;
-    if (in.numel() == 0) {
-      return stager.from_comm(at::empty(outsizes, in.options()));
-    }
-    // World of one: nothing crosses a wire, so nothing is compressed — the
-    // result is an exact clone. force_full_path (GPU) runs the whole
-    // pipeline instead: quantize, self-exchange, mx8_reduce_to.
-    if (P == 1 && !(config().force_full_path && in.is_cuda())) {
-      return stager.from_comm(fast_clone(in));
-    }
+    if (in.numel() == 0) return at::empty(outsizes, in.options());
+    // full path: quantize, self-exchange, mx8_reduce_to
+    if (world1_shortcut(tr, in)) return fast_clone(in);
     const auto g = axis_geom(in, axis);
     const int64_t count = g.axis / P;
     const int64_t L = g.before * count * g.after;
@@ -2278,10 +2276,9 @@ Tensor Communicator::ReducescatterCompressed(const Tensor& input,
       }
       move_axis_blocks(in, axis, displs, counts, blocks, /*pack=*/true);
     }
-    return stager.from_comm(mx8_reducescatter(tr, packed, L).view(outsizes));
-  }();
-  attach_history(result, grad_fn);
-  return result;
+    return mx8_reducescatter(tr, packed, L).view(outsizes);
+  };
+  return collective_frame(*this, input, make_grad_fn, body);
 }
 
 // ---------------------------------------------------------------------------
@@ -2308,31 +2305,16 @@ struct AllgatherCompressedBackward : public M4ANode {
 } // namespace
 
 Tensor Communicator::AllgatherCompressed(const Tensor& input, int64_t axis) {
-  TORCH_CHECK(input.scalar_type() == at::kFloat ||
-                  input.scalar_type() == at::kBFloat16 ||
-                  input.scalar_type() == at::kHalf,
-              "mpi4torch_amd: AllgatherCompressed supports float32, "
-              "bfloat16 and float16 tensors, got ", input.scalar_type());
+  check_mx8_input("AllgatherCompressed", input);
   axis = at::maybe_wrap_dim(axis, input.dim());
-  std::shared_ptr<M4ANode> grad_fn;
-  if (torch::autograd::compute_requires_grad(input)) {
-    grad_fn = make_node<AllgatherCompressedBackward>(
-        c10::intrusive_ptr<Communicator>::unsafe_reclaim_from_nonowning(this),
-        axis);
-    grad_fn->set_next_edges(torch::autograd::collect_next_edges(input));
-  }
-  auto result = [&]() {
-    at::AutoDispatchBelowADInplaceOrView guard;
-    DeviceStager stager(input);
-    auto in = stager.to_comm(input).contiguous().variable_data();
-    auto& tr = tr_for(in);
+  auto make_grad_fn = [&](auto comm) {
+    return make_node<AllgatherCompressedBackward>(comm, axis);
+  };
+  auto body = [&](Transport& tr, const Tensor& in,
+                  const DeviceStager&) -> Tensor {
     const int P = tr.size();
-    // World of one: nothing crosses a wire, so nothing is compressed — the
-    // result is an exact clone. force_full_path (GPU) runs the whole
-    // pipeline instead: quantize, 1-rank allgather, mx8_dequantize_blocks.
-    if (P == 1 && !(config().force_full_path && in.is_cuda())) {
-      return stager.from_comm(fast_clone(in));
-    }
+    // full path: quantize, 1-rank allgather, mx8_dequantize_blocks
+    if (world1_shortcut(tr, in)) return fast_clone(in);
     debug_check_axis_collective(group_name_, "AllgatherCompressed", in,
                                 {axis}, {axis});
     const auto g = axis_geom(in, axis);
@@ -2346,14 +2328,10 @@ Tensor Communicator::AllgatherCompressed(const Tensor& input, int64_t axis) {
                 "counts");
     auto outsizes = in.sizes().vec();
     outsizes[axis] = g.axis * P;
-    if (in.numel() == 0) {
-      return stager.from_comm(at::empty(outsizes, in.options()));
-    }
-    return stager.from_comm(
-        mx8_allgather(tr, in, g.before, g.axis * g.after).view(outsizes));
-  }();
-  attach_history(result, grad_fn);
-  return result;
+    if (in.numel() == 0) return at::empty(outsizes, in.options());
+    return mx8_allgather(tr, in, g.before, g.axis * g.after).view(outsizes);
+  };
+  return collective_frame(*this, input, make_grad_fn, body);
 }
 
 // ---------------------------------------------------------------------------
@@ -2383,42 +2361,27 @@ struct AlltoallCompressedBackward : public M4ANode {
 Tensor Communicator::AlltoallCompressed(const Tensor& input,
                                         int64_t gatheraxis,
                                         int64_t scatteraxis) {
-  TORCH_CHECK(input.scalar_type() == at::kFloat ||
-                  input.scalar_type() == at::kBFloat16 ||
-                  input.scalar_type() == at::kHalf,
-              "mpi4torch_amd: AlltoallCompressed supports float32, "
-              "bfloat16 and float16 tensors, got ", input.scalar_type());
+  check_mx8_input("AlltoallCompressed", input);
   gatheraxis = at::maybe_wrap_dim(gatheraxis, input.dim());
   scatteraxis = at::maybe_wrap_dim(scatteraxis, input.dim());
   TORCH_CHECK(gatheraxis != scatteraxis,
               "mpi4torch_amd: AlltoallCompressed requires two different "
               "axes, got ", gatheraxis, " for both; Alltoall handles the "
               "same-axis repartition");
-  std::shared_ptr<M4ANode> grad_fn;
-  if (torch::autograd::compute_requires_grad(input)) {
-    grad_fn = make_node<AlltoallCompressedBackward>(
-        c10::intrusive_ptr<Communicator>::unsafe_reclaim_from_nonowning(this),
-        gatheraxis, scatteraxis);
-    grad_fn->set_next_edges(torch::autograd::collect_next_edges(input));
-  }
-  auto result = [&]() {
-    at::AutoDispatchBelowADInplaceOrView guard;
-    DeviceStager stager(input);
-    auto in = stager.to_comm(input).contiguous().variable_data();
-    auto& tr = tr_for(in);
+  auto make_grad_fn = [&](auto comm) {
+    return make_node<AlltoallCompressedBackward>(comm, gatheraxis,
+                                                 scatteraxis);
+  };
+  auto body = [&](Transport& tr, const Tensor& in,
+                  const DeviceStager&) -> Tensor {
     const int P = tr.size();
     TORCH_CHECK(in.size(scatteraxis) % P == 0,
                 "mpi4torch_amd: AlltoallCompressed requires equal counts: "
                 "the scatter-axis size (", in.size(scatteraxis), ") must be "
                 "a multiple of the world size (", P, "); Alltoall/Alltoallv "
                 "handle variable counts");
-    // World of one: nothing crosses a wire, so nothing is compressed — the
-    // result is an exact clone. force_full_path (GPU) runs the whole
-    // pipeline instead: mx8_quantize_blocks, self-exchange,
-    // mx8_dequantize_blocks.
-    if (P == 1 && !(config().force_full_path && in.is_cuda())) {
-      return stager.from_comm(fast_clone(in));
-    }
+    // full path: mx8_quantize_blocks, self-exchange, mx8_dequantize_blocks
+    if (world1_shortcut(tr, in)) return fast_clone(in);
     debug_check_axis_collective(group_name_, "AlltoallCompressed", in,
                                 {gatheraxis}, {gatheraxis, scatteraxis});
     const int64_t g = in.size(gatheraxis);
@@ -2434,9 +2397,7 @@ Tensor Communicator::AlltoallCompressed(const Tensor& input,
     auto outsizes = in.sizes().vec();
     outsizes[scatteraxis] = n;
     outsizes[gatheraxis] = g * P;
-    if (in.numel() == 0) {
-      return stager.from_comm(at::empty(outsizes, in.options()));
-    }
+    if (in.numel() == 0) return at::empty(outsizes, in.options());
     // send side: `in` as [before_s][P][n*after_s]; receive side: the block
     // shape (scatter axis at n, gather axis at g) split at the gather axis
     const auto gs = axis_geom(in, scatteraxis);
@@ -2446,12 +2407,10 @@ Tensor Communicator::AlltoallCompressed(const Tensor& input,
       if (d < gatheraxis) before_g *= sz;
       if (d > gatheraxis) after_g *= sz;
     }
-    return stager.from_comm(mx8_alltoall(tr, in, gs.before, n * gs.after,
-                                         before_g, g * after_g)
-                                .view(outsizes));
-  }();
-  attach_history(result, grad_fn);
-  return result;
+    return mx8_alltoall(tr, in, gs.before, n * gs.after, before_g, g * after_g)
+        .view(outsizes);
+  };
+  return collective_frame(*this, input, make_grad_fn, body);
 }
 
 // ---------------------------------------------------------------------------
@@ -2934,11 +2893,7 @@ Tensor Communicator::AlltoallPairwiseCompressed(
     const Tensor& input, int64_t axis, std::vector<int64_t> send_counts,
     std::vector<int64_t> recv_counts, c10::optional<Tensor> send_order,
     c10::optional<Tensor> recv_order) {
-  TORCH_CHECK(input.scalar_type() == at::kFloat ||
-                  input.scalar_type() == at::kBFloat16 ||
-                  input.scalar_type() == at::kHalf,
-              "mpi4torch_amd: AlltoallPairwiseCompressed supports float32, "
-              "bfloat16 and float16 tensors, got ", input.scalar_type());
+  check_mx8_input("AlltoallPairwiseCompressed", input);
   axis = at::maybe_wrap_dim(axis, input.dim());
   auto& tr0 = cpu_tr();
   const int P = tr0.size();
@@ -2971,17 +2926,12 @@ Tensor Communicator::AlltoallPairwiseCompressed(
   check_pairwise_order("send_order", send_order, s_total, input);
   check_pairwise_order("recv_order", recv_order, r_total, input);
 
-  std::shared_ptr<M4ANode> grad_fn;
-  if (torch::autograd::compute_requires_grad(input)) {
-    grad_fn = make_node<AlltoallPairwiseCompressedBackward>(
-        c10::intrusive_ptr<Communicator>::unsafe_reclaim_from_nonowning(this),
-        axis, send_counts, recv_counts, send_order, recv_order);
-    grad_fn->set_next_edges(torch::autograd::collect_next_edges(input));
-  }
-  auto result = [&]() {
-    at::AutoDispatchBelowADInplaceOrView guard;
-    DeviceStager stager(input);
-    auto in = stager.to_comm(input).contiguous().variable_data();
+  auto make_grad_fn = [&](auto comm) {
+    return make_node<AlltoallPairwiseCompressedBackward>(
+        comm, axis, send_counts, recv_counts, send_order, recv_order);
+  };
+  auto body = [&](Transport& tr, const Tensor& in,
+                  const DeviceStager& stager) -> Tensor {
     // the order tensors follow the input through the stager
     c10::optional<Tensor> so, ro;
     if (send_order.has_value()) {
@@ -2990,35 +2940,30 @@ Tensor Communicator::AlltoallPairwiseCompressed(
     if (recv_order.has_value()) {
       ro = stager.to_comm(*recv_order).contiguous().variable_data();
     }
-    auto& tr = tr_for(in);
     auto outsizes = in.sizes().vec();
     outsizes[axis] = r_total;
-    // World of one: nothing crosses a wire, so nothing is compressed — the
-    // result is the exact permutation. force_full_path runs the whole
-    // pipeline instead: mx8_quantize_segments, self-exchange,
+    // World of one: the result is the exact permutation, under the rule of
+    // the uncompressed collectives — force_full_path runs the whole pipeline
+    // on either device: mx8_quantize_segments, self-exchange,
     // mx8_dequantize_segments.
-    if (tr.size() == 1 && !config().force_full_path) {
+    if (w1_shortcut(tr)) {
       auto y = so.has_value() ? in.index_select(axis, *so) : fast_clone(in);
       if (ro.has_value()) {
         auto out = at::empty(outsizes, in.options());
         out.index_copy_(axis, *ro, y);
         y = out;
       }
-      return stager.from_comm(std::move(y));
+      return y;
     }
     debug_check_axis_collective(group_name_, "AlltoallPairwiseCompressed",
                                 in, {axis}, {axis});
     const auto g = axis_geom(in, axis);
-    if (g.before * g.after == 0) {
-      return stager.from_comm(at::empty(outsizes, in.options()));
-    }
-    return stager.from_comm(
-        mx8_alltoall_pairwise(tr, in, g.before, g.after, send_counts,
-                              recv_counts, so, ro)
-            .view(outsizes));
-  }();
-  attach_history(result, grad_fn);
-  return result;
+    if (g.before * g.after == 0) return at::empty(outsizes, in.options());
+    return mx8_alltoall_pairwise(tr, in, g.before, g.after, send_counts,
+                                 recv_counts, so, ro)
+        .view(outsizes);
+  };
+  return collective_frame(*this, input, make_grad_fn, body);
 }
 
 // ---------------------------------------------------------------------------
@@ -3476,6 +3421,32 @@ Tensor debug_arith_reduce(const Tensor& own, const Tensor& staged, int64_t me,
   return out;
 }
 
+namespace {
+// The canary tests' caller buffers: the codec writes the first `need`
+// elements in place. `what` names that count in the binding's message.
+void check_canary_out(const char* binding, const Tensor& o, int64_t need,
+                      at::ScalarType dtype, const at::Device& dev,
+                      const char* what) {
+  TORCH_CHECK(o.dim() == 1 && o.is_contiguous() && o.numel() >= need &&
+                  o.scalar_type() == dtype && o.device() == dev,
+              binding, ": out must be a flat contiguous tensor of the "
+              "requested dtype with at least ", what, " elements");
+}
+
+void check_canary_wire(const char* binding, const Tensor& po, const Tensor& so,
+                       int64_t groups, const at::Device& dev,
+                       const char* what) {
+  auto ok = [&](const Tensor& t, int64_t need) {
+    return t.dim() == 1 && t.is_contiguous() &&
+           t.scalar_type() == at::kByte && t.numel() >= need &&
+           t.device() == dev;
+  };
+  TORCH_CHECK(ok(po, groups * 32) && ok(so, groups), binding,
+              ": payload_out and scales_out must be flat contiguous uint8 "
+              "tensors with at least ", what, " elements");
+}
+} // namespace
+
 std::tuple<Tensor, Tensor> debug_mx8_quantize(const Tensor& x) {
   auto ps = mx8_quantize(x.contiguous().view({-1}));
   return std::make_tuple(ps.first, ps.second);
@@ -3513,21 +3484,9 @@ Tensor debug_mx8_dequantize(const Tensor& payload, const Tensor& scales,
   auto pay = payload.contiguous().view({-1});
   auto sc = scales.contiguous().view({-1});
   if (!out.has_value()) return mx8_dequantize(pay, sc, numel, dtype);
-  // write the first `numel` elements of a caller buffer (canary tests)
-  const Tensor& o = *out;
-  TORCH_CHECK(o.dim() == 1 && o.is_contiguous() && o.numel() >= numel &&
-                  o.scalar_type() == dtype && o.device() == pay.device(),
-              "debug_mx8_dequantize: out must be a flat contiguous tensor "
-              "of the requested dtype with at least numel elements");
-  auto head = o.narrow(0, 0, numel);
-  if (pay.is_cuda()) {
-    launch_mx8_dequantize(pay.data_ptr(), sc.data_ptr(), head.data_ptr(),
-                          numel, mx8_dtype_code(dtype),
-                          current_gpu_stream(pay));
-  } else {
-    head.copy_(mx8_dequantize(pay, sc, numel, dtype));
-  }
-  return head;
+  check_canary_out("debug_mx8_dequantize", *out, numel, dtype, pay.device(),
+                   "numel");
+  return mx8_dequantize(pay, sc, numel, dtype, out->narrow(0, 0, numel));
 }
 
 Tensor debug_mx8_reduce_to(const Tensor& payload, const Tensor& scales,
@@ -3545,21 +3504,9 @@ Tensor debug_mx8_reduce_to(const Tensor& payload, const Tensor& scales,
   auto sin = scales.contiguous().view({-1});
   const int P = (int)scales.size(0);
   if (!out.has_value()) return mx8_reduce_to(pin, sin, numel, P, dtype);
-  // write the first `numel` elements of a caller buffer (canary tests)
-  const Tensor& o = *out;
-  TORCH_CHECK(o.dim() == 1 && o.is_contiguous() && o.numel() >= numel &&
-                  o.scalar_type() == dtype && o.device() == pin.device(),
-              "debug_mx8_reduce_to: out must be a flat contiguous tensor "
-              "of the requested dtype with at least numel elements");
-  auto head = o.narrow(0, 0, numel);
-  if (pin.is_cuda()) {
-    launch_mx8_reduce_to(pin.data_ptr(), sin.data_ptr(), head.data_ptr(),
-                         numel, P, mx8_dtype_code(dtype),
-                         current_gpu_stream(pin));
-  } else {
-    head.copy_(mx8_reduce_to(pin, sin, numel, P, dtype));
-  }
-  return head;
+  check_canary_out("debug_mx8_reduce_to", *out, numel, dtype, pin.device(),
+                   "numel");
+  return mx8_reduce_to(pin, sin, numel, P, dtype, out->narrow(0, 0, numel));
 }
 
 Tensor debug_mx8_dequantize_blocks(const Tensor& payload,
@@ -3582,25 +3529,12 @@ Tensor debug_mx8_dequantize_blocks(const Tensor& payload,
   if (!out.has_value()) {
     return mx8_dequantize_blocks(pin, sin, P, rows, row_elems, dtype);
   }
-  // write the first rows*P*row_elems elements of a caller buffer (canary
-  // tests)
   const int64_t total = rows * P * row_elems;
-  const Tensor& o = *out;
-  TORCH_CHECK(o.dim() == 1 && o.is_contiguous() && o.numel() >= total &&
-                  o.scalar_type() == dtype && o.device() == pin.device(),
-              "debug_mx8_dequantize_blocks: out must be a flat contiguous "
-              "tensor of the requested dtype with at least rows*P*row_elems "
-              "elements");
-  auto head = o.narrow(0, 0, total).view({rows, (int64_t)P, row_elems});
-  if (pin.is_cuda()) {
-    launch_mx8_dequantize_blocks(pin.data_ptr(), sin.data_ptr(),
-                                 head.data_ptr(), P, rows, row_elems,
-                                 mx8_dtype_code(dtype),
-                                 current_gpu_stream(pin));
-  } else {
-    head.copy_(mx8_dequantize_blocks(pin, sin, P, rows, row_elems, dtype));
-  }
-  return head;
+  check_canary_out("debug_mx8_dequantize_blocks", *out, total, dtype,
+                   pin.device(), "rows*P*row_elems");
+  return mx8_dequantize_blocks(
+      pin, sin, P, rows, row_elems, dtype,
+      out->narrow(0, 0, total).view({rows, (int64_t)P, row_elems}));
 }
 
 std::tuple<Tensor, Tensor> debug_mx8_quantize_blocks(
@@ -3620,32 +3554,14 @@ std::tuple<Tensor, Tensor> debug_mx8_quantize_blocks(
     auto ps = mx8_quantize_blocks(x, P, rows, row_elems);
     return std::make_tuple(ps.first, ps.second);
   }
-  // write the heads of caller buffers (canary tests)
   const int64_t Gb = (rows * row_elems + 31) / 32;
-  const Tensor& po = *payload_out;
-  const Tensor& so = *scales_out;
-  TORCH_CHECK(po.dim() == 1 && po.is_contiguous() &&
-                  po.scalar_type() == at::kByte &&
-                  po.numel() >= nblocks * Gb * 32 &&
-                  po.device() == x.device() && so.dim() == 1 &&
-                  so.is_contiguous() && so.scalar_type() == at::kByte &&
-                  so.numel() >= nblocks * Gb && so.device() == x.device(),
-              "debug_mx8_quantize_blocks: payload_out and scales_out must be "
-              "flat contiguous uint8 tensors with at least P*Gb*32 and P*Gb "
-              "elements");
-  auto ph = po.narrow(0, 0, nblocks * Gb * 32).view({nblocks, Gb * 32});
-  auto sh = so.narrow(0, 0, nblocks * Gb).view({nblocks, Gb});
-  if (x.is_cuda()) {
-    launch_mx8_quantize_blocks(x.data_ptr(), ph.data_ptr(), sh.data_ptr(), P,
-                               rows, row_elems,
-                               mx8_dtype_code(x.scalar_type()),
-                               current_gpu_stream(x));
-  } else {
-    auto ps = mx8_quantize_blocks(x, P, rows, row_elems);
-    ph.copy_(ps.first);
-    sh.copy_(ps.second);
-  }
-  return std::make_tuple(ph, sh);
+  check_canary_wire("debug_mx8_quantize_blocks", *payload_out, *scales_out,
+                    nblocks * Gb, x.device(), "P*Gb*32 and P*Gb");
+  auto ps = mx8_quantize_blocks(
+      x, P, rows, row_elems,
+      payload_out->narrow(0, 0, nblocks * Gb * 32).view({nblocks, Gb * 32}),
+      scales_out->narrow(0, 0, nblocks * Gb).view({nblocks, Gb}));
+  return std::make_tuple(ps.first, ps.second);
 }
 
 std::tuple<Tensor, Tensor> debug_mx8_quantize_segments(
@@ -3673,19 +3589,9 @@ std::tuple<Tensor, Tensor> debug_mx8_quantize_segments(
                 "must equal the number of slices ", S);
   }
   if (payload_out.has_value()) {
-    // write the heads of caller buffers (canary tests)
-    const Tensor& po = *payload_out;
-    const Tensor& so = *scales_out;
-    TORCH_CHECK(po.dim() == 1 && po.is_contiguous() &&
-                    po.scalar_type() == at::kByte &&
-                    po.numel() >= pl.total_groups * 32 &&
-                    po.device() == x.device() && so.dim() == 1 &&
-                    so.is_contiguous() && so.scalar_type() == at::kByte &&
-                    so.numel() >= pl.total_groups &&
-                    so.device() == x.device(),
-                "debug_mx8_quantize_segments: payload_out and scales_out "
-                "must be flat contiguous uint8 tensors with at least "
-                "32*sum(G) and sum(G) elements");
+    check_canary_wire("debug_mx8_quantize_segments", *payload_out,
+                      *scales_out, pl.total_groups, x.device(),
+                      "32*sum(G) and sum(G)");
   }
   auto ps = mx8_quantize_segments(x, rows, after, counts, order, payload_out,
                                   scales_out);
@@ -3724,15 +3630,10 @@ Tensor debug_mx8_dequantize_segments(const Tensor& payload,
     return mx8_dequantize_segments(payload, scales, rows, after, counts, order,
                                    dtype);
   }
-  // write the first rows*R*after elements of a caller buffer (canary tests)
   const int64_t total = rows * pl.slices * after;
-  const Tensor& o = *out;
-  TORCH_CHECK(o.dim() == 1 && o.is_contiguous() && o.numel() >= total &&
-                  o.scalar_type() == dtype && o.device() == payload.device(),
-              "debug_mx8_dequantize_segments: out must be a flat contiguous "
-              "tensor of the requested dtype with at least rows*R*after "
-              "elements");
-  auto head = o.narrow(0, 0, total).view({rows, pl.slices, after});
+  check_canary_out("debug_mx8_dequantize_segments", *out, total, dtype,
+                   payload.device(), "rows*R*after");
+  auto head = out->narrow(0, 0, total).view({rows, pl.slices, after});
   return mx8_dequantize_segments(payload, scales, rows, after, counts, order,
                                  dtype, head);
 }
