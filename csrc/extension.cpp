@@ -60,6 +60,8 @@ static auto communicator_class =
         .def("AlltoallPairwise", &Communicator::AlltoallPairwise)
         .def("AlltoallPairwiseCompressed",
              &Communicator::AlltoallPairwiseCompressed)
+        .def("AlltoallPairwiseCompressedIndexed",
+             &Communicator::AlltoallPairwiseCompressedIndexed)
         .def("Iallreduce", &Communicator::Iallreduce)
         .def("Ireducescatter", &Communicator::Ireducescatter)
         .def("Iallgather", &Communicator::Iallgather)
@@ -142,6 +144,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("after"), py::arg("counts"), py::arg("dtype"),
         py::arg("order") = c10::optional<at::Tensor>(),
         py::arg("out") = c10::optional<at::Tensor>());
+  m.def("_mx8_dequantize_combine", &m4a::debug_mx8_dequantize_combine,
+        py::arg("payload"), py::arg("scales"), py::arg("after"),
+        py::arg("counts"), py::arg("index"), py::arg("out_size"),
+        py::arg("fan"), py::arg("dtype"),
+        py::arg("out") = c10::optional<at::Tensor>());
+  m.def("_mx8_combine_table", &m4a::debug_mx8_combine_table,
+        py::arg("index"), py::arg("after"), py::arg("counts"),
+        py::arg("out_size"), py::arg("fan"));
   m.attr("_MX8_MAX_SEGS_PER_LAUNCH") = (int64_t)m4a::kMaxMx8SegsPerLaunch;
   m.def("reload_config",&m4a::reload_config_from_env);
 

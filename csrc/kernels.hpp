@@ -179,5 +179,20 @@ void launch_mx8_dequantize_segments(const void* payload, const void* scales,
                                     const Mx8SegDesc* segs, int nsegs,
                                     int64_t rows, int64_t S, int64_t after,
                                     int dtype, hipStream_t stream);
+// The top-k pairwise all-to-all tail: the reduce side of the above for
+// rows == 1. `out` is [out_slices][after] contiguous of `dtype`; `src` is a
+// device table [out_slices][fan] whose entries are the payload byte offset of
+// the first element of one received slice (32*goff_p + c*after for stream
+// slice c of segment p), or -1. Per output element, in fp32:
+//   acc = dq(src[s][0]), or +0.0 when that entry is -1;
+//   acc = acc + dq(src[s][j]) for j = 1..fan-1 in that order, -1 skipped;
+// then one RNE cast. A 255 scale or a NaN payload byte makes its own elements
+// NaN and no others. Writes exactly out_slices*after elements, zeros where a
+// slice has no source. The caller guarantees that every entry >= 0 names
+// `after` payload bytes inside the payload.
+void launch_mx8_dequantize_combine(const void* payload, const void* scales,
+                                   const int64_t* src, void* out,
+                                   int64_t out_slices, int fan, int64_t after,
+                                   int dtype, hipStream_t stream);
 
 } // namespace m4a

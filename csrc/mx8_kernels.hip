@@ -14,7 +14,7 @@
 //     hardware RNE f32->e4m3 of hip_fp8.h, which cannot saturate because
 //     amax*2^-E <= 448 by construction.
 //
-// Eight streaming kernels, all 256-thread workgroups, grid-stride, 16-byte
+// Nine streaming kernels, all 256-thread workgroups, grid-stride, 16-byte
 // accesses on the wide side, nontemporal (every byte is touched once):
 //   quantize   : 8 lanes x 16 B per fp32 group, 4 lanes x 16 B per 16-bit
 //                group; amax crosses the lanes with 3 / 2 xor-shuffles;
@@ -42,6 +42,10 @@
 //                variable slice counts (grid.y = segment, descriptors by
 //                value), optionally gathering / scattering slices through
 //                an int64 index while they read / write.
+//   dequantize_combine : the top-k tail — received slices that name the same
+//                output slice are summed there in table order in fp32 and
+//                cast once; flat grid over the output chunks, the sources'
+//                loads issued four at a time (see there).
 // The first four have a one-thread-per-group scalar twin for base pointers
 // that miss the vector alignment (e.g. a contiguous x[1:] view); the partial
 // last group of their vector kernels goes through the same scalar group
@@ -1029,6 +1033,108 @@ __global__ __launch_bounds__(256) void mx8_dequantize_segments_kernel_scalar(
   }
 }
 
+// ---- dequantize_combine (the top-k pairwise all-to-all tail) --------------
+//
+// The reduce side of the segments tail: several received slices name the
+// same output slice and are summed there. The output is [out_slices][after];
+// src is an int64 table [out_slices][fan] whose entries are the payload byte
+// offset of a received slice's first element, or -1. Segments are streams of
+// consecutive elements that start at payload byte 32*goff, so element a of a
+// slice at offset o has payload byte o + a and scale byte (o + a) >> 5: the
+// kernel needs no descriptor and no segment lookup. Rule, per output element:
+//   acc = dq(src[s][0]), or +0.0 when that entry is -1;
+//   acc = acc + dq(src[s][j]) for j = 1..fan-1 in that order, -1 skipped;
+//   one RNE cast.
+// All in fp32; a 255 scale or a NaN payload byte makes its own elements NaN
+// through the sum and no others. Exactly out_slices*after elements are
+// written, zeros where a slice has no source.
+//
+// Vector body (after % EPL == 0, out aligned to 16 bytes, payload to EPL): a
+// flat grid-stride loop over the out_slices*after/EPL output chunks, one
+// division by the chunks per slice. The table entries are plain cached
+// 8-byte loads, shared by all chunks of a slice. A slice offset is a
+// multiple of EPL (32*goff + c*after), so a chunk's EPL payload bytes are one
+// aligned load inside one group. The sources are taken kCombineBatch at a
+// time by a compile-time unroll: the table entries, then every payload and
+// scale load of the batch, are issued before the first value is consumed, so
+// a lane keeps up to four payload loads in flight for its one 16-byte store
+// and the staging stays in registers.
+constexpr int kCombineBatch = 4;
+
+template <int K, typename I>
+__global__ __launch_bounds__(256) void mx8_dequantize_combine_kernel(
+    const u8* __restrict__ pay, const u8* __restrict__ sc,
+    const long long* __restrict__ src, void* __restrict__ out, I chunks,
+    I cps, int fan) {
+  constexpr int EPL = kEPL<K>;
+  const I stride = (I)gridDim.x * blockDim.x;
+  for (I i = (I)blockIdx.x * blockDim.x + threadIdx.x; i < chunks;
+       i += stride) {
+    const I s = i / cps;
+    const long long col = (long long)(i - s * cps) * EPL;
+    const long long* __restrict__ t = src + (long long)s * fan;
+    float acc[EPL];
+    for (int k = 0; k < EPL; ++k) acc[k] = 0.0f;
+    for (int j0 = 0; j0 < fan; j0 += kCombineBatch) {
+      long long o[kCombineBatch];
+      unsigned w[kCombineBatch][EPL / 4];
+      int sb[kCombineBatch];
+#pragma unroll
+      for (int u = 0; u < kCombineBatch; ++u) {
+        o[u] = j0 + u < fan ? t[j0 + u] : -1;
+      }
+#pragma unroll
+      for (int u = 0; u < kCombineBatch; ++u) {
+        if (o[u] >= 0) {
+          const long long b = o[u] + col;
+          load_payload<EPL>(pay, b / EPL, w[u]);
+          sb[u] = sc[b >> 5];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kCombineBatch; ++u) {
+        if (o[u] >= 0) {
+          // source 0 is assigned (it keeps a -0.0), the others are added
+          const bool first = u == 0 && j0 == 0;
+          for (int d = 0; d < EPL / 4; ++d) {
+            for (int k = 0; k < 4; ++k) {
+              const float v = mx8_dequant((u8)(w[u][d] >> (8 * k)), sb[u]);
+              acc[4 * d + k] = first ? v : acc[4 * d + k] + v;
+            }
+          }
+        }
+      }
+    }
+    __builtin_nontemporal_store(pack16<K, EPL>(acc),
+                                reinterpret_cast<v4u*>(out) + i);
+  }
+}
+
+// General twin: any `after`, any alignment of the bases. One thread per
+// output element with the same source loop; token rows never take it.
+template <int K>
+__global__ __launch_bounds__(256) void mx8_dequantize_combine_kernel_scalar(
+    const u8* __restrict__ pay, const u8* __restrict__ sc,
+    const long long* __restrict__ src, void* __restrict__ out,
+    long long total, long long after, int fan) {
+  using T = typename Elem<K>::type;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+       e < total; e += stride) {
+    const long long s = e / after;
+    const long long a = e - s * after;
+    const long long* __restrict__ t = src + s * fan;
+    float acc = 0.0f;
+    for (int j = 0; j < fan; ++j) {
+      const long long o = t[j];
+      if (o < 0) continue;
+      const float v = mx8_dequant(pay[o + a], sc[(o + a) >> 5]);
+      acc = j == 0 ? v : acc + v;
+    }
+    reinterpret_cast<T*>(out)[e] = f32_to_elem<K>(acc);
+  }
+}
+
 inline unsigned grid_for(long long work) {
   long long blocks = (work + 255) / 256;
   if (blocks > 4096) blocks = 4096;
@@ -1345,7 +1451,45 @@ void launch_segments_t(std::conditional_t<Q, const void, void>* tensor,
   }
 }
 
+template <int K>
+void launch_dequantize_combine_t(const u8* pay, const u8* sc,
+                                 const long long* src, void* out,
+                                 int64_t out_slices, int fan, int64_t after,
+                                 hipStream_t stream) {
+  constexpr int EPL = kEPL<K>;
+  // Every slice offset is 32*goff + c*after, a multiple of EPL when after
+  // is, so a payload base aligned to EPL keeps every chunk's load aligned.
+  if (after % EPL == 0 && aligned(out, 16) && aligned(pay, EPL)) {
+    const long long cps = after / EPL;
+    const long long chunks = out_slices * cps;
+    by_width(chunks, [&](auto i) {
+      using I = decltype(i);
+      hipLaunchKernelGGL((mx8_dequantize_combine_kernel<K, I>),
+                         dim3(grid_for(chunks)), dim3(256), 0, stream, pay, sc,
+                         src, out, (I)chunks, (I)cps, fan);
+    });
+  } else {
+    const long long total = out_slices * after;
+    hipLaunchKernelGGL((mx8_dequantize_combine_kernel_scalar<K>),
+                       dim3(grid_for(total)), dim3(256), 0, stream, pay, sc,
+                       src, out, total, (long long)after, fan);
+  }
+}
+
 } // namespace
+
+void launch_mx8_dequantize_combine(const void* payload, const void* scales,
+                                   const int64_t* src, void* out,
+                                   int64_t out_slices, int fan, int64_t after,
+                                   int dtype, hipStream_t stream) {
+  if (out_slices <= 0 || after <= 0 || fan <= 0) return;
+  by_dtype(dtype, [&](auto k) {
+    launch_dequantize_combine_t<k>(static_cast<const u8*>(payload),
+                                   static_cast<const u8*>(scales),
+                                   reinterpret_cast<const long long*>(src),
+                                   out, out_slices, fan, after, stream);
+  });
+}
 
 void launch_mx8_quantize_segments(const void* in, const int64_t* idx,
                                   void* payload, void* scales,

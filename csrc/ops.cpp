@@ -1324,6 +1324,150 @@ Tensor mx8_alltoall_pairwise(Transport& tr, const Tensor& in, int64_t rows,
                                  recv_order, in.scalar_type());
 }
 
+// ---- the top-k tail: received slices summed where several name one slice ---
+//
+// Rule (normative; mx8_dequantize_combine_kernel matches it bit for bit): a
+// table [out_size, fan] lists for every output slice its sources in order,
+// -1 for none. Per output element, in fp32:
+//   acc = v(tab[s][0]), or +0.0 when that entry is -1;
+//   acc = acc + v(tab[s][j]) for j = 1..fan-1 in that order, -1 skipped;
+// then one cast.
+
+// The table of `index` (int64 [R], index[i] = output slice of source i):
+// the sources of a slice in ascending i, each entered as base[i] (int64 [R],
+// >= 0). Built with torch ops on index's device, without a host sync: a
+// stable argsort groups the sources of a destination in ascending i, the
+// rank inside the destination is the sorted position minus the first
+// occurrence. Entries with index outside [0, out_size) or rank >= fan are
+// dropped: they are written to one spare dump slot at the end of the
+// allocation, so nothing out of contract forms an address outside it.
+// Returns the flat allocation [out_size*fan + 1]; the table is its head.
+Tensor mx8_combine_table(const Tensor& index, const Tensor& base,
+                         int64_t out_size, int64_t fan) {
+  const int64_t R = index.numel();
+  auto table = at::full({out_size * fan + 1}, -1, index.options());
+  if (R == 0) return table;
+  auto valid = index.ge(0).logical_and(index.lt(out_size));
+  // out-of-range entries sort behind every destination
+  auto key = at::where(valid, index, at::full_like(index, out_size));
+  auto sorted = at::sort(key, /*stable=*/true, /*dim=*/0, /*descending=*/false);
+  const Tensor& dest = std::get<0>(sorted);
+  const Tensor& perm = std::get<1>(sorted);
+  auto rank = at::arange(R, index.options()) -
+              at::searchsorted(dest, dest, /*out_int32=*/false,
+                               /*right=*/false);
+  auto keep = dest.lt(out_size).logical_and(rank.lt(fan));
+  auto slot = at::where(keep, dest * fan + rank,
+                        at::full_like(dest, out_size * fan));
+  table.scatter_(0, slot, base.index_select(0, perm));
+  return table;
+}
+
+// The kernel's table: every source entered as the payload byte offset of its
+// slice, 32*goff_p + c*after for slice c of segment p. The offsets are one
+// arange per non-empty segment: the segment plan lives on the host and
+// nothing is uploaded.
+Tensor mx8_combine_offsets_table(const Tensor& index, const Mx8SegPlan& pl,
+                                 int64_t after, int64_t out_size,
+                                 int64_t fan) {
+  auto base = at::empty({pl.slices}, index.options());
+  for (const auto& s : pl.segs) {
+    if (s.count == 0) continue;
+    auto part = base.narrow(0, s.displ, s.count);
+    at::arange_out(part, 32 * s.goff, 32 * s.goff + s.count * after, after);
+  }
+  return mx8_combine_table(index, base, out_size, fan);
+}
+
+// The rule above on values v [R, after] fp32 through a table [out_size, fan]
+// of row numbers: [out_size, after] fp32, not yet cast.
+Tensor ordered_table_sum(const Tensor& v, const Tensor& tab) {
+  const int64_t out_size = tab.size(0), fan = tab.size(1);
+  auto acc = at::zeros({out_size, v.size(1)}, v.options());
+  if (v.size(0) == 0) return acc;
+  for (int64_t j = 0; j < fan; ++j) {
+    auto col = tab.select(1, j);
+    auto ok = col.ge(0).unsqueeze(1);
+    auto term = v.index_select(0, col.clamp_min(0));
+    acc = at::where(ok, j == 0 ? term : acc + term, acc);
+  }
+  return acc;
+}
+
+// The top-k tail of the pairwise all-to-all (rows == 1): the received
+// segments' streams (layout as mx8_dequantize_segments, R = sum(counts)
+// received slices of `after` elements) are dequantized and received slice i
+// is added into output slice index[i] under the rule above, sources in
+// ascending i; slices no entry names are zeros. Returns [out_size, after] of
+// `dtype`, written into `out_opt` when given. At most `fan` sources per
+// slice: surplus and out-of-range entries are dropped.
+Tensor mx8_dequantize_combine(const Tensor& pay, const Tensor& sc,
+                              int64_t after,
+                              const std::vector<int64_t>& counts,
+                              const Tensor& index, int64_t out_size,
+                              int64_t fan, at::ScalarType dtype,
+                              const c10::optional<Tensor>& out_opt =
+                                  c10::nullopt) {
+  const int dt = mx8_dtype_code(dtype);
+  const auto pl = mx8_seg_plan(counts, 1, after);
+  auto iopts = index.options();
+  if (pay.is_cuda()) {
+    auto out = out_or_empty(out_opt, {out_size, after},
+                            pay.options().dtype(dtype));
+    auto table = mx8_combine_offsets_table(index, pl, after, out_size, fan);
+    launch_mx8_dequantize_combine(pay.data_ptr(), sc.data_ptr(),
+                                  table.data_ptr<int64_t>(), out.data_ptr(),
+                                  out_size, (int)fan, after, dt,
+                                  current_gpu_stream(pay));
+    return out;
+  }
+  std::vector<Tensor> parts;
+  for (size_t p = 0; p < counts.size(); ++p) {
+    if (pl.groups[p] == 0) continue;
+    const int64_t G = pl.groups[p];
+    parts.push_back(
+        mx8_dequantize_groups(
+            pay.narrow(0, pl.segs[p].goff * 32, G * 32).view({G, 32}),
+            sc.narrow(0, pl.segs[p].goff, G))
+            .view({-1})
+            .narrow(0, 0, counts[p] * after));
+  }
+  auto v = parts.empty() ? at::zeros({0, after}, pay.options().dtype(at::kFloat))
+                         : at::cat(parts).view({pl.slices, after});
+  auto table = mx8_combine_table(index, at::arange(pl.slices, iopts), out_size,
+                                 fan);
+  auto res = ordered_table_sum(
+                 v, table.narrow(0, 0, out_size * fan).view({out_size, fan}))
+                 .to(dtype);
+  return out_opt.has_value() ? out_opt->copy_(res) : res;
+}
+
+// mx8_alltoall_pairwise for the top-k case: the head gathers through
+// send_index, which may repeat slices (the quantize kernel never needed an
+// injective index); with a recv_index the tail is mx8_dequantize_combine
+// (rows == 1), without one the plain segments tail.
+Tensor mx8_alltoall_pairwise_indexed(
+    Transport& tr, const Tensor& in, int64_t rows, int64_t after,
+    const std::vector<int64_t>& send_counts,
+    const std::vector<int64_t>& recv_counts,
+    const c10::optional<Tensor>& send_index,
+    const c10::optional<Tensor>& recv_index, int64_t out_size, int64_t fan) {
+  const auto sp = mx8_seg_plan(send_counts, rows, after);
+  const auto rp = mx8_seg_plan(recv_counts, rows, after);
+  auto q = mx8_quantize_segments(in, rows, after, send_counts, send_index);
+  auto bopts = in.options().dtype(at::kByte);
+  auto stg_pay = at::empty({rp.total_groups * 32}, bopts);
+  auto stg_sc = at::empty({rp.total_groups}, bopts);
+  mx8_exchange(tr, {q.first, q.second, sp.goffs(), sp.groups},
+               {stg_pay, stg_sc, rp.goffs(), rp.groups});
+  if (!recv_index.has_value()) {
+    return mx8_dequantize_segments(stg_pay, stg_sc, rows, after, recv_counts,
+                                   c10::nullopt, in.scalar_type());
+  }
+  return mx8_dequantize_combine(stg_pay, stg_sc, after, recv_counts,
+                                *recv_index, out_size, fan, in.scalar_type());
+}
+
 // The mxfp8 sibling of hierarchical_allreduce: quantize once, exchange each
 // rank's copy of group-block j to rank j (payload and scales as two
 // contiguous pieces per peer in ONE grouped call), fused
@@ -2967,6 +3111,172 @@ Tensor Communicator::AlltoallPairwiseCompressed(
 }
 
 // ---------------------------------------------------------------------------
+// AlltoallPairwiseCompressedIndexed (MI355X extension; not in the reference
+// API): the top-k form of AlltoallPairwiseCompressed. The send index may
+// repeat slices (a gather) and the receive index may name a slice several
+// times (an ordered scatter-add): dispatch and combine of a top-k MoE layer
+// and both their backwards are this one op.
+// ---------------------------------------------------------------------------
+
+namespace {
+struct AlltoallPairwiseCompressedIndexedBackward : public M4ANode {
+  AlltoallPairwiseCompressedIndexedBackward(
+      int64_t axis, std::vector<int64_t> send, std::vector<int64_t> recv,
+      c10::optional<Tensor> send_index, c10::optional<Tensor> recv_index,
+      int64_t in_size, int64_t max_repeat)
+      : axis(axis), send(std::move(send)), recv(std::move(recv)),
+        send_index(std::move(send_index)), recv_index(std::move(recv_index)),
+        in_size(in_size), max_repeat(max_repeat) {}
+  std::string name() const override {
+    return "M4AAlltoallPairwiseCompressedIndexedBackward";
+  }
+  variable_list apply(variable_list&& grads) override {
+    variable_list out(1);
+    if (should_compute_output(0)) {
+      // exact adjoint of gather -> exchange -> scatter-add: counts and
+      // indices swap, the gather's adjoint sums into the input's slices;
+      // quantization is straight-through
+      out[0] = comm->AlltoallPairwiseCompressedIndexed(
+          grads[0], axis, recv, send, recv_index, send_index,
+          send_index.has_value() ? c10::optional<int64_t>(in_size)
+                                 : c10::nullopt,
+          max_repeat);
+    }
+    return out;
+  }
+  int64_t axis;
+  std::vector<int64_t> send, recv;
+  c10::optional<Tensor> send_index, recv_index;
+  int64_t in_size, max_repeat;
+};
+
+// Shape, dtype and device always; range and the repeat bound on the CPU,
+// and on the GPU only under the desync detector's debug mode (they cost a
+// sync).
+void check_pairwise_index(const char* which,
+                          const c10::optional<Tensor>& index, int64_t len,
+                          int64_t size, int64_t max_repeat,
+                          const Tensor& input) {
+  if (!index.has_value()) return;
+  const Tensor& o = *index;
+  TORCH_CHECK(o.dim() == 1 && o.numel() == len,
+              "AlltoallPairwiseCompressedIndexed: ", which, " must be a 1-D "
+              "tensor of length ", len, " (the sum of its counts), got shape ",
+              o.sizes());
+  TORCH_CHECK(o.scalar_type() == at::kLong,
+              "AlltoallPairwiseCompressedIndexed: ", which, " must be an "
+              "int64 tensor, got ", o.scalar_type());
+  TORCH_CHECK(o.device() == input.device(),
+              "AlltoallPairwiseCompressedIndexed: ", which, " must be on the "
+              "tensor's device ", input.device(), ", got ", o.device());
+  if (len > 0 && (!o.is_cuda() || config().debug_collectives)) {
+    TORCH_CHECK(o.min().item<int64_t>() >= 0 && o.max().item<int64_t>() < size,
+                "AlltoallPairwiseCompressedIndexed: ", which, " entries must "
+                "lie in [0, ", size, ")");
+    const int64_t most = at::bincount(o).max().item<int64_t>();
+    TORCH_CHECK(most <= max_repeat,
+                "AlltoallPairwiseCompressedIndexed: a slice occurs ", most,
+                " times in ", which, ", more than max_repeat = ", max_repeat);
+  }
+}
+} // namespace
+
+Tensor Communicator::AlltoallPairwiseCompressedIndexed(
+    const Tensor& input, int64_t axis, std::vector<int64_t> send_counts,
+    std::vector<int64_t> recv_counts, c10::optional<Tensor> send_index,
+    c10::optional<Tensor> recv_index, c10::optional<int64_t> out_size,
+    int64_t max_repeat) {
+  const char* who = "AlltoallPairwiseCompressedIndexed";
+  check_mx8_input(who, input);
+  axis = at::maybe_wrap_dim(axis, input.dim());
+  auto& tr0 = cpu_tr();
+  const int P = tr0.size();
+  TORCH_CHECK((int)send_counts.size() == P, who,
+              ": send_counts must have world_size entries");
+  if (recv_counts.empty() && P > 1) {
+    // exchange the count matrix; my recv from j = j's send to me
+    auto mat = host_allgather_int64_vec(group_name_, send_counts);
+    recv_counts.resize(P);
+    const int me = tr0.rank();
+    for (int j = 0; j < P; ++j) recv_counts[j] = mat[(int64_t)j * P + me];
+  }
+  if (P == 1 && recv_counts.empty()) recv_counts = send_counts;
+  TORCH_CHECK((int)recv_counts.size() == P, who,
+              ": recv_counts must have world_size entries");
+  int64_t s_total = 0, r_total = 0;
+  for (int64_t c : send_counts) {
+    TORCH_CHECK(c >= 0, who, ": negative send count ", c);
+    s_total += c;
+  }
+  for (int64_t c : recv_counts) {
+    TORCH_CHECK(c >= 0, who, ": negative recv count ", c);
+    r_total += c;
+  }
+  TORCH_CHECK(max_repeat >= 1, who, ": max_repeat must be >= 1, got ",
+              max_repeat);
+  const int64_t in_size = input.size(axis);
+  TORCH_CHECK(send_index.has_value() || in_size == s_total, who,
+              ": without a send_index the sum of send_counts (", s_total,
+              ") must equal the axis size (", in_size, ")");
+  TORCH_CHECK(!recv_index.has_value() || out_size.has_value(), who,
+              ": out_size is required with a recv_index");
+  TORCH_CHECK(!out_size.has_value() || *out_size >= 0, who,
+              ": out_size must be >= 0, got ", out_size.value_or(0));
+  const auto g0 = axis_geom(input, axis);
+  TORCH_CHECK(!recv_index.has_value() || g0.before == 1, who,
+              ": with a recv_index every dimension before the axis must have "
+              "size 1 (token tensors are [N, D]), got shape ", input.sizes(),
+              " with axis ", axis);
+  const int64_t n_out = recv_index.has_value() ? *out_size : r_total;
+  check_pairwise_index("send_index", send_index, s_total, in_size, max_repeat,
+                       input);
+  check_pairwise_index("recv_index", recv_index, r_total, n_out, max_repeat,
+                       input);
+
+  auto make_grad_fn = [&](auto comm) {
+    return make_node<AlltoallPairwiseCompressedIndexedBackward>(
+        comm, axis, send_counts, recv_counts, send_index, recv_index, in_size,
+        max_repeat);
+  };
+  auto body = [&](Transport& tr, const Tensor& in,
+                  const DeviceStager& stager) -> Tensor {
+    // the index tensors follow the input through the stager
+    c10::optional<Tensor> si, ri;
+    if (send_index.has_value()) {
+      si = stager.to_comm(*send_index).contiguous().variable_data();
+    }
+    if (recv_index.has_value()) {
+      ri = stager.to_comm(*recv_index).contiguous().variable_data();
+    }
+    auto outsizes = in.sizes().vec();
+    outsizes[axis] = n_out;
+    const auto g = axis_geom(in, axis);
+    // World of one: the exact, uncompressed result — the gather, then the
+    // ordered fp32 table sum on the values themselves, then the cast.
+    // force_full_path runs the whole pipeline on either device.
+    if (w1_shortcut(tr)) {
+      auto y = si.has_value() ? in.index_select(axis, *si) : fast_clone(in);
+      if (!ri.has_value()) return y;
+      auto table = mx8_combine_table(*ri, at::arange(r_total, ri->options()),
+                                     n_out, max_repeat);
+      return ordered_table_sum(
+                 y.view({r_total, g.after}).to(at::kFloat),
+                 table.narrow(0, 0, n_out * max_repeat)
+                     .view({n_out, max_repeat}))
+          .to(in.scalar_type())
+          .view(outsizes);
+    }
+    debug_check_axis_collective(group_name_, who, in, {axis}, {axis});
+    if (g.before * g.after == 0) return at::zeros(outsizes, in.options());
+    return mx8_alltoall_pairwise_indexed(tr, in, g.before, g.after,
+                                         send_counts, recv_counts, si, ri,
+                                         n_out, max_repeat)
+        .view(outsizes);
+  };
+  return collective_frame(*this, input, make_grad_fn, body);
+}
+
+// ---------------------------------------------------------------------------
 // Isend / Irecv / Wait (reference csrc/extension.cpp:1048-1265). The handle
 // is the same 3-tensor contract [meta, buffer, input]; the MPI_Request
 // becomes an entry in the request table (hipEvent on the p2p stream / c10d
@@ -3636,6 +3946,57 @@ Tensor debug_mx8_dequantize_segments(const Tensor& payload,
   auto head = out->narrow(0, 0, total).view({rows, pl.slices, after});
   return mx8_dequantize_segments(payload, scales, rows, after, counts, order,
                                  dtype, head);
+}
+
+Tensor debug_mx8_dequantize_combine(const Tensor& payload,
+                                    const Tensor& scales, int64_t after,
+                                    std::vector<int64_t> counts,
+                                    const Tensor& index, int64_t out_size,
+                                    int64_t fan, at::ScalarType dtype,
+                                    const c10::optional<Tensor>& out) {
+  TORCH_CHECK(after >= 1 && out_size >= 0 && fan >= 1,
+              "debug_mx8_dequantize_combine: after and fan must be >= 1 and "
+              "out_size >= 0");
+  const auto pl = mx8_seg_plan(counts, 1, after);
+  TORCH_CHECK(payload.dim() == 1 && scales.dim() == 1 &&
+                  payload.is_contiguous() && scales.is_contiguous() &&
+                  payload.scalar_type() == at::kByte &&
+                  scales.scalar_type() == at::kByte &&
+                  payload.numel() == pl.total_groups * 32 &&
+                  scales.numel() == pl.total_groups &&
+                  payload.device() == scales.device(),
+              "debug_mx8_dequantize_combine expects flat contiguous uint8 "
+              "payload [32*sum(G)] and scales [sum(G)]");
+  TORCH_CHECK(index.dim() == 1 && index.numel() == pl.slices &&
+                  index.scalar_type() == at::kLong && index.is_contiguous() &&
+                  index.device() == payload.device(),
+              "debug_mx8_dequantize_combine: index must be a contiguous "
+              "int64 tensor of sum(counts) entries on the payload's device");
+  if (!out.has_value()) {
+    return mx8_dequantize_combine(payload, scales, after, counts, index,
+                                  out_size, fan, dtype);
+  }
+  const int64_t total = out_size * after;
+  check_canary_out("debug_mx8_dequantize_combine", *out, total, dtype,
+                   payload.device(), "out_size*after");
+  auto head = out->narrow(0, 0, total).view({out_size, after});
+  return mx8_dequantize_combine(payload, scales, after, counts, index,
+                                out_size, fan, dtype, head);
+}
+
+Tensor debug_mx8_combine_table(const Tensor& index, int64_t after,
+                               std::vector<int64_t> counts, int64_t out_size,
+                               int64_t fan) {
+  const auto pl = mx8_seg_plan(counts, 1, after);
+  TORCH_CHECK(index.dim() == 1 && index.numel() == pl.slices &&
+                  index.scalar_type() == at::kLong && out_size >= 0 &&
+                  fan >= 1,
+              "debug_mx8_combine_table: index must be an int64 tensor of "
+              "sum(counts) entries, out_size >= 0 and fan >= 1");
+  return mx8_combine_offsets_table(index.contiguous(), pl, after, out_size,
+                                   fan)
+      .narrow(0, 0, out_size * fan)
+      .view({out_size, fan});
 }
 
 Tensor debug_pairloc_reduce(const Tensor& stacked, int64_t op) {

@@ -122,6 +122,25 @@ struct Communicator : torch::CustomClassHolder {
       std::vector<int64_t> recv_counts, c10::optional<at::Tensor> send_order,
       c10::optional<at::Tensor> recv_order);
 
+  // The top-k form of AlltoallPairwiseCompressed (MI355X extension).
+  // send_index (int64, any entries in [0, size(axis)), repeats included,
+  // length sum(send_counts)) gathers the slices that travel; without a
+  // recv_index the result is y as above. With recv_index (length
+  // sum(recv_counts)) and out_size the result has out_size slices and
+  // out[s] is the fp32 sum, in ascending i, of the received slices with
+  // recv_index[i] == s, cast once; slices nothing names are zeros. That form
+  // needs every dimension before `axis` to have size 1. No slice may occur
+  // more than max_repeat times in either index (checked on the CPU, on the
+  // GPU only in debug mode; surplus and out-of-range entries are dropped
+  // there). Backward: the same op on the gradient with counts and indices
+  // swapped and out_size = input.size(axis) — gather and ordered
+  // scatter-add are adjoints. A world of one returns the exact result.
+  at::Tensor AlltoallPairwiseCompressedIndexed(
+      const at::Tensor& input, int64_t axis, std::vector<int64_t> send_counts,
+      std::vector<int64_t> recv_counts, c10::optional<at::Tensor> send_index,
+      c10::optional<at::Tensor> recv_index, c10::optional<int64_t> out_size,
+      int64_t max_repeat);
+
   // Non-blocking allreduce (MI355X-first overlap primitive, not in the
   // reference API): returns a wait handle; no autograd through it — use
   // Allreduce for differentiable paths. Gradient bucketing (parallel/ddp)
@@ -237,6 +256,20 @@ at::Tensor debug_mx8_dequantize_segments(
     int64_t after, std::vector<int64_t> counts, at::ScalarType dtype,
     const c10::optional<at::Tensor>& order,
     const c10::optional<at::Tensor>& out);
+// the top-k pairwise all-to-all tail (rows == 1): the segments' streams ->
+// [out_size, after] of dtype, received slice i added into slice index[i] in
+// fp32 in ascending i (at most `fan` per slice), one cast; slices nothing
+// names are zeros, out-of-range and surplus entries are dropped. With `out`
+// (flat, of dtype) the result aliases its head.
+at::Tensor debug_mx8_dequantize_combine(
+    const at::Tensor& payload, const at::Tensor& scales, int64_t after,
+    std::vector<int64_t> counts, const at::Tensor& index, int64_t out_size,
+    int64_t fan, at::ScalarType dtype, const c10::optional<at::Tensor>& out);
+// the table the kernel of the above reads, [out_size, fan] payload byte
+// offsets or -1, built on index's device
+at::Tensor debug_mx8_combine_table(const at::Tensor& index, int64_t after,
+                                   std::vector<int64_t> counts,
+                                   int64_t out_size, int64_t fan);
 // staging: flat P rank-major blocks of [rows, row_elems]; out: contiguous
 // [rows, P, row_elems]. The axis unpack of an equal-count Allgather.
 void debug_unpack_blocks(const at::Tensor& staging, const at::Tensor& out);

@@ -11,7 +11,7 @@ block-scaled fp8 wire with the token permutes fused into the codec kernels
 (AlltoallPairwiseCompressed); the default run is unchanged.
 
 Run: torchrun --standalone --local-addr 127.0.0.1 --nproc-per-node 2 \
-        examples/expert_parallel_moe.py [--compression mxfp8]
+        examples/expert_parallel_moe.py [--compression mxfp8] [--top-k 2]
 """
 
 import argparse
@@ -27,6 +27,9 @@ from mpi4torch_amd.models.moe import ExpertParallelMoE
 ap = argparse.ArgumentParser()
 ap.add_argument("--compression", choices=["mxfp8"], default=None,
                 help="send tokens over the mxfp8 wire")
+ap.add_argument("--top-k", type=int, default=1,
+                help="experts per token (with --compression mxfp8, k > 1 "
+                     "uses AlltoallPairwiseCompressedIndexed)")
 args = ap.parse_args()
 
 device = torch.device("cuda") if torch.cuda.is_available() else torch.device("cpu")
@@ -35,7 +38,8 @@ comm = m4a.COMM_WORLD
 torch.manual_seed(4)  # router + this rank's experts (router identical everywhere)
 d_model, n_experts = 32, 4 * comm.size
 moe = ExpertParallelMoE(d_model, n_experts,
-                        compression=args.compression).to(device)
+                        compression=args.compression,
+                        top_k=args.top_k).to(device)
 opt = torch.optim.AdamW(moe.parameters(), lr=1e-3)
 
 torch.manual_seed(500 + comm.rank)  # per-rank token stream

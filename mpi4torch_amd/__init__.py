@@ -382,6 +382,56 @@ class MPI_Communicator:
         return self._comm.AlltoallPairwiseCompressed(
             tensor, axis, send_counts, recv_counts, send_order, recv_order)
 
+    def AlltoallPairwiseCompressedIndexed(
+            self, tensor: torch.Tensor, axis: int, send_counts: List[int],
+            recv_counts: List[int],
+            send_index: Optional[torch.Tensor] = None,
+            recv_index: Optional[torch.Tensor] = None,
+            out_size: Optional[int] = None,
+            max_repeat: int = 1) -> torch.Tensor:
+        """The top-k form of AlltoallPairwiseCompressed (MI355X extension):
+        the send index may repeat slices and the receive index may name a
+        slice several times, which sums the slices that arrive for it.
+        Dispatch and combine of a top-k mixture-of-experts layer, and both
+        their backwards, are this one op.
+
+        ``xs = tensor.index_select(axis, send_index)``, or ``tensor``
+        without a ``send_index``. ``send_index`` is a 1-D int64 tensor on
+        the tensor's device of length ``sum(send_counts)``; any entries in
+        ``[0, tensor.size(axis))`` are allowed, repeats included. Without it
+        ``sum(send_counts)`` must be the axis size. Counts, quantization and
+        the exchange work exactly as in AlltoallPairwiseCompressed; the
+        gather rides inside the quantize kernel.
+
+        Without ``recv_index`` the result is ``y``, the received blocks in
+        rank order. With ``recv_index`` (length ``sum(recv_counts)``) and
+        ``out_size`` the result has ``out_size`` slices on the axis:
+        ``out[s]`` is the sum of the received slices i with
+        ``recv_index[i] == s``, added in float32 in ascending i and cast once
+        to the tensor's dtype; a slice nothing names is zero. One fused
+        gfx950 kernel reads the wire bytes and writes the result: no
+        ``[sum(recv_counts), D]`` buffer exists and no atomics are involved,
+        so the result is deterministic. This form needs every dimension
+        before ``axis`` to have size 1 (token tensors are ``[N, D]``).
+
+        No slice index may occur more than ``max_repeat`` times in either
+        index (k for top-k routing). That and the range are checked for CPU
+        tensors, and for GPU tensors only under MPI4TORCH_AMD_DEBUG=1;
+        otherwise the GPU path drops surplus and out-of-range receive
+        entries and reads an out-of-range send entry as zeros.
+
+        A world of one returns the exact, uncompressed result.
+
+        Backward: the same op on the gradient with the counts and the two
+        indices swapped and ``out_size = tensor.size(axis)`` — the exact
+        adjoint of gather, exchange and scatter-add, quantization
+        straight-through. A ``send_index`` therefore needs the size-1
+        leading dimensions too once gradients flow.
+        """
+        return self._comm.AlltoallPairwiseCompressedIndexed(
+            tensor, axis, send_counts, recv_counts, send_index, recv_index,
+            out_size, max_repeat)
+
     def Iallreduce(self, tensor: torch.Tensor, op: int) -> WaitHandle:
         """Non-blocking Allreduce (no autograd): returns a WaitHandle whose
         Wait() yields the reduced tensor. The overlap primitive behind

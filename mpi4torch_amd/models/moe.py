@@ -15,6 +15,16 @@ permutation into the dequantize kernel on the way back, so the layer loses
 two full passes over the tokens as well as wire bytes. Expert ids stay on the
 uncompressed AlltoallPairwise because they must arrive exact. The default
 None leaves the layer bit for bit as it was.
+
+top_k > 1 routes every token to its k best experts (topk of the softmax
+gates, not renormalised). The N*k assignments are sorted by owner; expert ids
+and assignment gates travel uncompressed, the owner scales its expert output
+by the received gate, and the combine sums a token's k results. With
+compression="mxfp8" both transfers are AlltoallPairwiseCompressedIndexed: the
+dispatch gathers token order // k while it quantizes and the combine adds the
+k received rows of a token in fp32 while it dequantizes, so neither the
+gathered tokens nor an [N*k, D] combine buffer is materialised. top_k=1 takes
+the two top-1 paths above, untouched.
 """
 
 import torch
@@ -24,13 +34,18 @@ import mpi4torch_amd as m4a
 
 class ExpertParallelMoE(torch.nn.Module):
     def __init__(self, d_model: int, n_experts: int, comm=None,
-                 d_hidden: int = None, compression=None):
+                 d_hidden: int = None, compression=None, top_k: int = 1):
         super().__init__()
         if compression not in (None, "mxfp8"):
             raise ValueError(
                 "mpi4torch_amd ExpertParallelMoE: compression must be None "
                 f"or 'mxfp8', got {compression!r}")
+        if not 1 <= top_k <= n_experts:
+            raise ValueError(
+                "mpi4torch_amd ExpertParallelMoE: top_k must lie in "
+                f"[1, n_experts = {n_experts}], got {top_k!r}")
         self.compression = compression
+        self.top_k = top_k
         self.comm = comm if comm is not None else m4a.COMM_WORLD
         P = self.comm.size
         assert n_experts % P == 0, (
@@ -51,6 +66,8 @@ class ExpertParallelMoE(torch.nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """x: [N, D] local tokens -> [N, D]."""
+        if self.top_k > 1:
+            return self._forward_topk(x)
         if self.compression is not None:
             return self._forward_compressed(x)
         N, D = x.shape
@@ -96,9 +113,7 @@ class ExpertParallelMoE(torch.nn.Module):
         y = combined.index_select(0, inverse)
         return y * gate.unsqueeze(1)
 
-    def _forward_compressed(self, x: torch.Tensor) -> torch.Tensor:
-        """forward() over the mxfp8 wire: both token permutes ride inside
-        the codec kernels of AlltoallPairwiseCompressed."""
+    def _check_mx8_params(self):
         ok = (torch.float32, torch.bfloat16, torch.float16)
         for name, p in self.named_parameters():
             if p.dtype not in ok:
@@ -106,6 +121,68 @@ class ExpertParallelMoE(torch.nn.Module):
                     "mpi4torch_amd ExpertParallelMoE: compression='mxfp8' "
                     "needs float32, bfloat16 or float16 parameters, got "
                     f"{p.dtype} for {name}")
+
+    def _run_experts(self, dispatched, local_eid):
+        out = torch.zeros_like(dispatched)
+        for e in range(self.experts_per_rank):
+            mask = local_eid == e
+            if bool(mask.any()):
+                idx = mask.nonzero(as_tuple=True)[0]
+                out = out.index_copy(
+                    0, idx, self.experts[e](dispatched.index_select(0, idx)))
+        return out
+
+    def _forward_topk(self, x: torch.Tensor) -> torch.Tensor:
+        """forward() for top_k > 1: N*k assignments, sorted by owner."""
+        mx8 = self.compression is not None
+        if mx8:
+            self._check_mx8_params()
+        N, D = x.shape
+        P, k = self.comm.size, self.top_k
+        gates = torch.softmax(self.router(x), dim=-1)
+        gate, expert = gates.topk(k, dim=-1)          # [N, k] each
+        expert = expert.reshape(-1)                   # assignment n*k + j
+        owner = expert // self.experts_per_rank
+        order = torch.argsort(owner, stable=True)     # assignments by owner
+        tok = order // k                              # their tokens
+        send_counts = torch.bincount(owner, minlength=P).tolist()
+        recv_counts = self._recv_counts(send_counts)
+
+        # dispatch: stream slice i is token tok[i]; a token travels k times
+        if mx8:
+            dispatched = self.comm.AlltoallPairwiseCompressedIndexed(
+                x, 0, send_counts, recv_counts, send_index=tok, max_repeat=k)
+        else:
+            dispatched = self.comm.AlltoallPairwise(
+                x.index_select(0, tok), 0, send_counts, recv_counts)
+        # expert ids and gates must arrive exact: uncompressed. The gate
+        # keeps its autograd path, so the router needs no custom backward.
+        eid = self.comm.AlltoallPairwise(
+            expert.index_select(0, order).to(torch.float64).unsqueeze(1), 0,
+            send_counts, recv_counts).squeeze(1).long()
+        g = self.comm.AlltoallPairwise(
+            gate.reshape(-1).index_select(0, order).unsqueeze(1), 0,
+            send_counts, recv_counts)
+        local_eid = eid - self.comm.rank * self.experts_per_rank
+
+        # the owner applies the gate, which keeps the wire op linear
+        out = self._run_experts(dispatched, local_eid) * g
+
+        # combine: a token's k results are summed where they arrive
+        if mx8:
+            return self.comm.AlltoallPairwiseCompressedIndexed(
+                out, 0, recv_counts, send_counts, recv_index=tok, out_size=N,
+                max_repeat=k)
+        combined = self.comm.AlltoallPairwise(out, 0, recv_counts,
+                                              send_counts)
+        inverse = torch.empty_like(order)
+        inverse[order] = torch.arange(N * k, device=x.device)
+        return combined.index_select(0, inverse).view(N, k, D).sum(1)
+
+    def _forward_compressed(self, x: torch.Tensor) -> torch.Tensor:
+        """forward() over the mxfp8 wire: both token permutes ride inside
+        the codec kernels of AlltoallPairwiseCompressed."""
+        self._check_mx8_params()
         P = self.comm.size
         logits = self.router(x)
         gates = torch.softmax(logits, dim=-1)

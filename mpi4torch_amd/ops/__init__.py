@@ -98,6 +98,19 @@ def alltoall_pairwise_compressed(tensor: torch.Tensor, axis: int, send_counts,
         send_order, recv_order)
 
 
+def alltoall_pairwise_compressed_indexed(tensor: torch.Tensor, axis: int,
+                                         send_counts, recv_counts=None,
+                                         send_index=None, recv_index=None,
+                                         out_size=None, max_repeat=1,
+                                         comm=None):
+    """Pairwise-count all-to-all over an mxfp8 wire for top-k routing: a
+    gather with repeats on the way out, an ordered fp32 sum on the way in."""
+    return _comm(comm).AlltoallPairwiseCompressedIndexed(
+        tensor, axis, list(send_counts),
+        [] if recv_counts is None else list(recv_counts),
+        send_index, recv_index, out_size, max_repeat)
+
+
 def iallreduce(tensor: torch.Tensor, op: Optional[int] = None, comm=None):
     return _comm(comm).Iallreduce(tensor, _m.MPI_SUM if op is None else op)
 

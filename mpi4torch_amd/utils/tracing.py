@@ -167,6 +167,16 @@ class TracedCommunicator:
                 tensor, axis, send_counts, recv_counts, send_order,
                 recv_order))
 
+    def AlltoallPairwiseCompressedIndexed(self, tensor, axis, send_counts,
+                                          recv_counts, send_index=None,
+                                          recv_index=None, out_size=None,
+                                          max_repeat=1):
+        return self._record(
+            "AlltoallPairwiseCompressedIndexed", tensor,
+            lambda: self._comm.AlltoallPairwiseCompressedIndexed(
+                tensor, axis, send_counts, recv_counts, send_index,
+                recv_index, out_size, max_repeat))
+
     def Iallreduce(self, tensor, op):
         return self._record("Iallreduce", tensor,
                             lambda: self._comm.Iallreduce(tensor, op))

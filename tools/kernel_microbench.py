@@ -10,6 +10,7 @@ reported GB/s counts actual bytes touched. Run on an MI355X box:
     python tools/kernel_microbench.py --mx8-dequantize-blocks   # only that part
     python tools/kernel_microbench.py --mx8-quantize-blocks     # only that part
     python tools/kernel_microbench.py --mx8-segments            # only that part
+    python tools/kernel_microbench.py --mx8-combine             # only that part
 
 The mxfp8 section times the three codec kernels and, in the same run and
 alternating with it, the sibling fp8_reduce kernel at the same P and n, so
@@ -23,6 +24,8 @@ fused all-to-all head mx8_quantize_blocks against the axis pack into staging
 plus mx8_quantize. The segments part does the same for the pairwise
 all-to-all head and tail with a fused token permute, mx8_quantize_segments
 and mx8_dequantize_segments, against index_select plus the flat codec kernel.
+The combine part times the top-k tail mx8_dequantize_combine against
+mx8_dequantize_segments plus a torch gather-and-sum or index_add_.
 """
 
 import os
@@ -512,6 +515,68 @@ def mx8_segments_section(repeats=5):
         C.force_full_path(False)
 
 
+def mx8_combine_section(repeats=5):
+    """mx8_dequantize_combine at the top-2 MoE combine geometry: 64Ki tokens
+    x 4096, k = 2, so 128Ki received slices in the 8 uneven segments of the
+    section above, a random assignment, bf16 and fp32. The fused kernel (its
+    table build included, and the table build alone) against
+    mx8_dequantize_segments without an index followed by
+      (i)  index_select(0, inverse).view(N, k, D).sum(1), and
+      (ii) zeros.index_add_,
+    alternating in the same run, 5 repeats of 30 launches each. Bytes of the
+    fused kernel: 33/32*N*k*D wire bytes in, N*D*esize out."""
+    C = m._C
+    med = lambda v: sorted(v)[len(v) // 2]
+    N, D, k = 64 << 10, 4096, 2
+    counts = [20000, 0, 12000, 24000, 8000, 30000, 17072, 20000]
+    R = N * k
+    assert sum(counts) == R
+    gen = torch.Generator(device="cuda").manual_seed(11)
+    # received slice i belongs to token tok[i]; every token k times
+    tok = torch.randperm(R, device="cuda", generator=gen) // k
+    inverse = torch.argsort(tok, stable=True)    # token n's slices, ascending
+    pay, sc = C._mx8_quantize(
+        (torch.randn(R, D, device="cuda") * 0.2).to(torch.bfloat16).view(-1))
+    for dtype, tag in ((torch.bfloat16, "bf16"), (torch.float32, "fp32")):
+        es = torch.empty(0, dtype=dtype).element_size()
+        runs = {
+            "fused mx8_dequantize_combine (with table)":
+                lambda: C._mx8_dequantize_combine(pay, sc, D, counts, tok, N,
+                                                  k, dtype),
+            "table build alone":
+                lambda: C._mx8_combine_table(tok, D, counts, N, k),
+            "(i) dequantize_segments + index_select.sum":
+                lambda: C._mx8_dequantize_segments(pay, sc, 1, D, counts,
+                                                   dtype)
+                .view(R, D).index_select(0, inverse).view(N, k, D).sum(1),
+            "(ii) dequantize_segments + index_add_":
+                lambda: torch.zeros(N, D, device="cuda", dtype=dtype)
+                .index_add_(0, tok, C._mx8_dequantize_segments(
+                    pay, sc, 1, D, counts, dtype).view(R, D)),
+        }
+        times = {name: [] for name in runs}
+        for _ in range(repeats):
+            for name, fn in runs.items():
+                times[name].append(timeit(fn))
+        for name, ts in times.items():
+            print(f"(combine {tag}) {name:44s} {med(ts)*1e3:9.1f} us  (min "
+                  f"{min(ts)*1e3:.1f} max {max(ts)*1e3:.1f} us, {len(ts)} "
+                  "repeats)", flush=True)
+        fused = med(times["fused mx8_dequantize_combine (with table)"])
+        seq = min(min(ts) for name, ts in times.items() if name[0] == "(")
+        nbytes = 33 * (R * D // 32) + N * D * es
+        print(f"(combine {tag}) fused {nbytes/fused/1e9:.2f} TB/s over "
+              f"{nbytes/2**20:.0f} MiB; fused median "
+              f"{'below' if fused < seq else 'NOT below'} the minimum of the "
+              f"faster sequence ({seq*1e3:.1f} us), ratio {fused/seq:.3f}",
+              flush=True)
+
+
+if "--mx8-combine" in sys.argv:
+    mx8_combine_section()
+    dist.destroy_process_group()
+    sys.exit(0)
+
 if "--mx8-segments" in sys.argv:
     mx8_segments_section()
     dist.destroy_process_group()
@@ -538,6 +603,7 @@ if "--mx8" in sys.argv:
     mx8_dequantize_blocks_section()
     mx8_quantize_blocks_section()
     mx8_segments_section()
+    mx8_combine_section()
     dist.destroy_process_group()
     sys.exit(0)
 
