@@ -62,6 +62,8 @@ static auto communicator_class =
              &Communicator::AlltoallPairwiseCompressed)
         .def("AlltoallPairwiseCompressedIndexed",
              &Communicator::AlltoallPairwiseCompressedIndexed)
+        .def("AlltoallPairwiseCompressedWeighted",
+             &Communicator::AlltoallPairwiseCompressedWeighted)
         .def("Iallreduce", &Communicator::Iallreduce)
         .def("Ireducescatter", &Communicator::Ireducescatter)
         .def("Iallgather", &Communicator::Iallgather)
@@ -148,6 +150,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("payload"), py::arg("scales"), py::arg("after"),
         py::arg("counts"), py::arg("index"), py::arg("out_size"),
         py::arg("fan"), py::arg("dtype"),
+        py::arg("out") = c10::optional<at::Tensor>());
+  m.def("_mx8_dequantize_combine_weighted",
+        &m4a::debug_mx8_dequantize_combine_weighted, py::arg("payload"),
+        py::arg("scales"), py::arg("after"), py::arg("counts"),
+        py::arg("index"), py::arg("weights"), py::arg("out_size"),
+        py::arg("fan"), py::arg("dtype"),
+        py::arg("out") = c10::optional<at::Tensor>());
+  m.def("_mx8_quantize_segments_weighted",
+        &m4a::debug_mx8_quantize_segments_weighted, py::arg("x"),
+        py::arg("after"), py::arg("counts"), py::arg("weights"),
+        py::arg("order") = c10::optional<at::Tensor>(),
+        py::arg("payload_out") = c10::optional<at::Tensor>(),
+        py::arg("scales_out") = c10::optional<at::Tensor>());
+  m.def("_mx8_dequantize_rowdot", &m4a::debug_mx8_dequantize_rowdot,
+        py::arg("payload"), py::arg("scales"), py::arg("after"),
+        py::arg("counts"), py::arg("index"), py::arg("g"),
         py::arg("out") = c10::optional<at::Tensor>());
   m.def("_mx8_combine_table", &m4a::debug_mx8_combine_table,
         py::arg("index"), py::arg("after"), py::arg("counts"),

@@ -194,5 +194,39 @@ void launch_mx8_dequantize_combine(const void* payload, const void* scales,
                                    const int64_t* src, void* out,
                                    int64_t out_slices, int fan, int64_t after,
                                    int dtype, hipStream_t stream);
+// The gated top-k tail: launch_mx8_dequantize_combine with an fp32 weight per
+// table entry, `wsrc` [out_slices][fan] parallel to `src`. Every entry is
+// loaded, so all of them must be initialised; one whose src entry is -1 is
+// never used. Per output element, in fp32:
+//   acc = fl(w0 * dq(src[s][0])), or +0.0 when that entry is -1;
+//   acc = acc + fl(w_j * dq(src[s][j])) for j = 1..fan-1, -1 skipped;
+// then one RNE cast. The product is rounded before the add (no FMA), so the
+// torch composite acc + w*v gives the same bits; NaN follows IEEE through the
+// product (0 * NaN is NaN).
+void launch_mx8_dequantize_combine_weighted(
+    const void* payload, const void* scales, const int64_t* src,
+    const float* wsrc, void* out, int64_t out_slices, int fan, int64_t after,
+    int dtype, hipStream_t stream);
+// launch_mx8_quantize_segments for rows == 1 with one fp32 weight per stream
+// slice (`weights` has sum(count_p) entries): stream slice displ_p + c is
+// fl32(weights[displ_p + c] * f32(in[slice(displ_p + c)])), one fp32 multiply
+// that never rounds to `dtype`; the group's amax is taken over the products.
+// An idx entry outside [0, S) reads as zeros before the product.
+void launch_mx8_quantize_segments_weighted(
+    const void* in, const int64_t* idx, const float* weights, void* payload,
+    void* scales, const Mx8SegDesc* segs, int nsegs, int64_t S, int64_t after,
+    int dtype, hipStream_t stream);
+// The gate gradient of the gated tail: for the R received slices of `after`
+// elements, slice i at payload byte base[i],
+//   gw[i] = sum_a dq(slice i)[a] * f32(g[idx[i]][a])     (fp32)
+// with g [out_slices][after] contiguous of `dtype`. idx[i] outside
+// [0, out_slices) gives exactly 0; a 255 scale or NaN payload byte makes its
+// own gw[i] NaN. Deterministic (no atomics); the order of association is the
+// kernel's. Writes exactly R floats.
+void launch_mx8_dequantize_rowdot(const void* payload, const void* scales,
+                                  const int64_t* base, const int64_t* idx,
+                                  const void* g, float* gw, int64_t R,
+                                  int64_t out_slices, int64_t after, int dtype,
+                                  hipStream_t stream);
 
 } // namespace m4a

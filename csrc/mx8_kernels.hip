@@ -46,6 +46,14 @@
 //                output slice are summed there in table order in fp32 and
 //                cast once; flat grid over the output chunks, the sources'
 //                loads issued four at a time (see there).
+// and the three kernels of the gated top-k combine:
+//   dequantize_combine_weighted : dequantize_combine with an fp32 weight per
+//                table entry, product rounded before the add;
+//   quantize_segments_weighted : quantize_segments (rows == 1) of slices
+//                scaled by an fp32 weight each, the head of its backward;
+//   dequantize_rowdot : the weights' gradient, one dot product per received
+//                slice over a group of 8 to 64 lanes; the one reduction here.
+// Each of them has a twin for any slice length and alignment.
 // The first four have a one-thread-per-group scalar twin for base pointers
 // that miss the vector alignment (e.g. a contiguous x[1:] view); the partial
 // last group of their vector kernels goes through the same scalar group
@@ -648,13 +656,20 @@ struct BlockMap {
 // need every lane). Slots from `chunks` on and missed chunks load nothing,
 // count as zeros in the amax and store zero payload, so the partial last
 // group needs no scalar tail. bs has any alignment: store_scales falls back
-// to per-lane bytes.
-template <int K, typename I, typename Map>
+// to per-lane bytes. pre(i, x) may rework the elements of stream chunk
+// i < chunks before they are quantized (the weighted head scales them).
+struct NoPre {
+  template <typename I, int N>
+  __device__ void operator()(I, float (&)[N]) const {}
+};
+
+template <int K, typename I, typename Map, typename Pre = NoPre>
 __device__ inline void quantize_stream(const void* __restrict__ in,
                                        u8* __restrict__ bp,
                                        u8* __restrict__ bs, long long G,
                                        I chunks, I slots, const Map& map,
-                                       I first, I stride) {
+                                       I first, I stride,
+                                       const Pre& pre = Pre{}) {
   constexpr int LPG = kLPG<K>;
   const int lane = threadIdx.x & 63;
   // i0: the wave's first slot (workgroups are whole waves)
@@ -664,6 +679,7 @@ __device__ inline void quantize_stream(const void* __restrict__ in,
     if (i < chunks) src = map(i);
     float x[kEPL<K>];
     load_chunk<K>(in, src, Map::kCanMiss ? src >= 0 : i < chunks, x);
+    if (i < chunks) pre(i, x);
     const int sb = quant_lane<K>(x, i < slots, bp, (long long)i);
     store_scales<LPG>(bs, (long long)(i0 / LPG), G, sb, lane);
   }
@@ -1033,6 +1049,91 @@ __global__ __launch_bounds__(256) void mx8_dequantize_segments_kernel_scalar(
   }
 }
 
+// ---- quantize_segments_weighted (the head of the weighted combine's
+// backward) ------------------------------------------------------------------
+//
+// quantize_segments for rows == 1 with one fp32 weight per stream slice:
+// stream slice c of segment p is fl32(w[displ_p + c] * f32(slice)), and the
+// group's amax is taken over the products. The product is a single fp32
+// multiply and never passes through the tensor's dtype.
+
+// One fp32 multiply / add, rounded on its own. The weighted kernels owe the
+// composite exactly these, so they are spelled as the single VALU
+// instruction: the compiler can neither contract a pair into an FMA nor fold
+// neighbours into the packed two-lane forms. Compiled for another target,
+// a plain a * b / a + b under contraction off is the fallback.
+__device__ inline float mul_single(float a, float b) {
+  float r;
+  asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ inline float add_single(float a, float b) {
+  float r;
+  asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+
+// pre() of quantize_stream: chunk i belongs to stream slice i / cps of the
+// segment, whose weight is one cached 4-byte load shared by the slice's
+// chunks (the division is the map's own).
+template <typename I>
+struct SliceWeight {
+  const float* __restrict__ w;  // the segment's first weight
+  I cps;
+  template <int N>
+  __device__ void operator()(I i, float (&x)[N]) const {
+    const float wi = w[i / cps];
+    for (int k = 0; k < N; ++k) x[k] = mul_single(wi, x[k]);
+  }
+};
+
+// MODE 0 (no index) or 1 of SegMap; with rows == 1 a segment's chunks are
+// its slices' chunks one after the other under both.
+template <int K, typename I, int MODE>
+__global__ __launch_bounds__(256) void mx8_quantize_segments_weighted_kernel(
+    const void* __restrict__ in, const long long* __restrict__ idx,
+    const float* __restrict__ wt, u8* __restrict__ pay, u8* __restrict__ sc,
+    SegArgs segs, long long S, I cps) {
+  if (segs.s[blockIdx.y].count == 0) return;
+  const SegMap<I, MODE> map(segs.s[blockIdx.y], idx, S, cps, 1);
+  const long long G = ((long long)map.chunks + kLPG<K> - 1) / kLPG<K>;
+  quantize_stream<K, I>(in, pay + map.goff * 32, sc + map.goff, G, map.chunks,
+                        (I)(G * kLPG<K>), map, MX8_GRID_STRIDE(I),
+                        SliceWeight<I>{wt + map.displ, cps});
+}
+
+// General twin: the segments twin's walk with the weight of the cursor's
+// stream slice.
+template <int K, bool IDX>
+__global__ __launch_bounds__(256)
+void mx8_quantize_segments_weighted_kernel_scalar(
+    const void* __restrict__ in, const long long* __restrict__ idx,
+    const float* __restrict__ wt, u8* __restrict__ pay, u8* __restrict__ sc,
+    SegArgs segs, long long S, long long after) {
+  using T = typename Elem<K>::type;
+  const Mx8SegDesc& d = segs.s[blockIdx.y];
+  if (d.count == 0) return;
+  SegCursor<IDX> cur(d, idx, S, after, 1);
+  const long long G = (cur.L + 31) / 32;
+  const T* __restrict__ src = reinterpret_cast<const T*>(in);
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < G;
+       g += stride) {
+    cur.seek(g * 32);
+    float x[32];
+    for (int k = 0; k < 32; ++k) {
+      x[k] = 0.0f;
+      if (cur.in_stream()) {
+        const long long o = cur.offset();
+        x[k] = mul_single(wt[d.displ + cur.c],
+                         o >= 0 ? elem_to_f32<K>(src[o]) : 0.0f);
+        cur.advance();
+      }
+    }
+    encode_group_scalar(x, pay + (d.goff + g) * 32, sc + d.goff + g);
+  }
+}
+
 // ---- dequantize_combine (the top-k pairwise all-to-all tail) --------------
 //
 // The reduce side of the segments tail: several received slices name the
@@ -1132,6 +1233,216 @@ __global__ __launch_bounds__(256) void mx8_dequantize_combine_kernel_scalar(
       acc = j == 0 ? v : acc + v;
     }
     reinterpret_cast<T*>(out)[e] = f32_to_elem<K>(acc);
+  }
+}
+
+// ---- dequantize_combine_weighted (the gated top-k tail) --------------------
+//
+// dequantize_combine with one fp32 weight per table entry: wsrc is a table
+// [out_slices][fan] parallel to src. The vector body loads a weight with its
+// offset, before it knows the offset's sign, so every entry must be
+// initialised; one whose offset is -1 is never used (the host writes 0).
+// Rule, per output element, in fp32:
+//   acc = fl(w0 * dq(src[s][0])), or +0.0 when that entry is -1;
+//   acc = acc + fl(w_j * dq(src[s][j])) for j = 1..fan-1, -1 skipped;
+//   one RNE cast.
+// The product is rounded before the add: mul_single and add_single are never
+// contracted, which is what lets the torch composite acc + w*v agree bit for
+// bit. A weight of 0 on a NaN source stays NaN (IEEE through the product).
+//
+// A sibling of mx8_dequantize_combine_kernel, not an instantiation of it, so
+// that kernel is compiled from the same text as before. Same layout: flat
+// grid over the output chunks, the batch's table entries (offset and weight,
+// both cached loads shared by a slice's chunks), then its payload and scale
+// loads, all issued before the first value is consumed.
+template <int K, typename I>
+__global__ __launch_bounds__(256) void mx8_dequantize_combine_weighted_kernel(
+    const u8* __restrict__ pay, const u8* __restrict__ sc,
+    const long long* __restrict__ src, const float* __restrict__ wsrc,
+    void* __restrict__ out, I chunks, I cps, int fan) {
+  constexpr int EPL = kEPL<K>;
+  const I stride = (I)gridDim.x * blockDim.x;
+  for (I i = (I)blockIdx.x * blockDim.x + threadIdx.x; i < chunks;
+       i += stride) {
+    const I s = i / cps;
+    const long long col = (long long)(i - s * cps) * EPL;
+    const long long* __restrict__ t = src + (long long)s * fan;
+    const float* __restrict__ tw = wsrc + (long long)s * fan;
+    float acc[EPL];
+    for (int k = 0; k < EPL; ++k) acc[k] = 0.0f;
+    for (int j0 = 0; j0 < fan; j0 += kCombineBatch) {
+      long long o[kCombineBatch];
+      float wj[kCombineBatch];
+      unsigned w[kCombineBatch][EPL / 4];
+      int sb[kCombineBatch];
+#pragma unroll
+      for (int u = 0; u < kCombineBatch; ++u) {
+        o[u] = j0 + u < fan ? t[j0 + u] : -1;
+        wj[u] = j0 + u < fan ? tw[j0 + u] : 0.0f;
+      }
+#pragma unroll
+      for (int u = 0; u < kCombineBatch; ++u) {
+        if (o[u] >= 0) {
+          const long long b = o[u] + col;
+          load_payload<EPL>(pay, b / EPL, w[u]);
+          sb[u] = sc[b >> 5];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kCombineBatch; ++u) {
+        if (o[u] >= 0) {
+          // source 0 is assigned (it keeps a -0.0), the others are added
+          const bool first = u == 0 && j0 == 0;
+          for (int d = 0; d < EPL / 4; ++d) {
+            for (int k = 0; k < 4; ++k) {
+              const float v = mul_single(
+                  wj[u], mx8_dequant((u8)(w[u][d] >> (8 * k)), sb[u]));
+              acc[4 * d + k] = first ? v : add_single(acc[4 * d + k], v);
+            }
+          }
+        }
+      }
+    }
+    __builtin_nontemporal_store(pack16<K, EPL>(acc),
+                                reinterpret_cast<v4u*>(out) + i);
+  }
+}
+
+// General twin: any `after`, any alignment of the bases.
+template <int K>
+__global__ __launch_bounds__(256)
+void mx8_dequantize_combine_weighted_kernel_scalar(
+    const u8* __restrict__ pay, const u8* __restrict__ sc,
+    const long long* __restrict__ src, const float* __restrict__ wsrc,
+    void* __restrict__ out, long long total, long long after, int fan) {
+  using T = typename Elem<K>::type;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+       e < total; e += stride) {
+    const long long s = e / after;
+    const long long a = e - s * after;
+    float acc = 0.0f;
+    for (int j = 0; j < fan; ++j) {
+      const long long o = src[s * fan + j];
+      if (o < 0) continue;
+      const float v = mul_single(wsrc[s * fan + j],
+                                mx8_dequant(pay[o + a], sc[(o + a) >> 5]));
+      acc = j == 0 ? v : add_single(acc, v);
+    }
+    reinterpret_cast<T*>(out)[e] = f32_to_elem<K>(acc);
+  }
+}
+
+// ---- dequantize_rowdot (the gate gradient of the weighted tail) -----------
+//
+// gw[i] = sum_a dq(received slice i)[a] * f32(g[index[i]][a]) for the R
+// received slices of `after` elements; base[i] is slice i's payload byte
+// offset (what the combine table is built from), g is [out_slices][after]
+// of the tensor dtype, gw is fp32. A slice whose index lies outside
+// [0, out_slices) gives exactly 0; a 255 scale or a NaN payload byte makes
+// its own slice's result NaN. A reduction, so unlike the stream kernels it
+// owns its order of association: fixed, hence the same bits on every run,
+// but not the composite's. No atomics, no LDS.
+//
+// Vector body (after % EPL == 0, g aligned to 16 bytes, payload to EPL): a
+// group of LPS lanes owns a slice, LPS in {8, 16, 32, 64} the smallest that
+// is not below the cps chunks of a slice, so a 64-element bf16 row fills 8
+// lanes and a wave does 8 slices at once, and a 4096-element one takes the
+// whole wave for 8 trips. A lane's trip is one chunk: EPL payload bytes, the
+// scale byte, the 16-byte chunk of g (a cached load: the k slices of a token
+// read the same row), EPL fused multiply-adds into one fp32 accumulator. Two
+// trips' loads are issued before the first is consumed. index[i] and base[i]
+// are loaded by the group's first lane and broadcast. The lanes then add up
+// by xor-shuffles below LPS and the first lane stores. Both loops have
+// wave-uniform trip counts (the slice loop runs on the wave's first slice,
+// the chunk loop on cps), so every lane is present at every shuffle; a lane
+// without a chunk, or of a slice past R or out of range, carries zeros.
+template <int K, int LPS, typename I>
+__global__ __launch_bounds__(256) void mx8_dequantize_rowdot_kernel(
+    const u8* __restrict__ pay, const u8* __restrict__ sc,
+    const long long* __restrict__ base, const long long* __restrict__ idx,
+    const void* __restrict__ g, float* __restrict__ gw, I R, I cps,
+    long long out_slices) {
+  constexpr int EPL = kEPL<K>;
+  constexpr int SPW = 64 / LPS;  // slices per wave
+  const int sub = threadIdx.x & (LPS - 1);
+  const I stride = (I)gridDim.x * (256 / LPS);
+  for (I s0 = ((I)blockIdx.x * 256 + (threadIdx.x & ~63)) / LPS; s0 < R;
+       s0 += stride) {
+    const I s = s0 + (I)((threadIdx.x & 63) / LPS);
+    long long t = -1, o = 0;
+    if (sub == 0 && s < R) {
+      t = idx[s];
+      o = base[s];
+    }
+    if constexpr (SPW == 1) {
+      t = __shfl(t, 0);
+      o = __shfl(o, 0);
+    } else {
+      t = __shfl(t, 0, LPS);
+      o = __shfl(o, 0, LPS);
+    }
+    const bool ok = (unsigned long long)t < (unsigned long long)out_slices;
+    const long long pslot = o / EPL;   // o is a multiple of EPL
+    const long long gslot = t * (long long)cps;
+    float acc = 0.0f;
+    for (I c0 = 0; c0 < cps; c0 += 2 * LPS) {
+      unsigned w[2][EPL / 4];
+      int sb[2];
+      v4u gv[2];
+      bool act[2];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const I c = c0 + (I)(u * LPS + sub);
+        act[u] = ok && c < cps;
+        if (act[u]) {
+          load_payload<EPL>(pay, pslot + (long long)c, w[u]);
+          sb[u] = sc[(o + (long long)c * EPL) >> 5];
+          gv[u] = reinterpret_cast<const v4u*>(g)[gslot + (long long)c];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        if (act[u]) {
+          float x[EPL];
+          unpack16<K, EPL>(gv[u], x);
+          for (int d = 0; d < EPL / 4; ++d) {
+            for (int k = 0; k < 4; ++k) {
+              acc = fmaf(mx8_dequant((u8)(w[u][d] >> (8 * k)), sb[u]),
+                         x[4 * d + k], acc);
+            }
+          }
+        }
+      }
+    }
+    for (int m = LPS / 2; m >= 1; m >>= 1) acc += __shfl_xor(acc, m);
+    if (sub == 0 && s < R) gw[s] = ok ? acc : 0.0f;
+  }
+}
+
+// General twin: any `after`, any alignment. One thread per slice walks its
+// elements in order.
+template <int K>
+__global__ __launch_bounds__(256) void mx8_dequantize_rowdot_kernel_scalar(
+    const u8* __restrict__ pay, const u8* __restrict__ sc,
+    const long long* __restrict__ base, const long long* __restrict__ idx,
+    const void* __restrict__ g, float* __restrict__ gw, long long R,
+    long long after, long long out_slices) {
+  using T = typename Elem<K>::type;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x; s < R;
+       s += stride) {
+    const long long t = idx[s];
+    float acc = 0.0f;
+    if ((unsigned long long)t < (unsigned long long)out_slices) {
+      const long long o = base[s];
+      const T* __restrict__ row = reinterpret_cast<const T*>(g) + t * after;
+      for (long long a = 0; a < after; ++a) {
+        acc = fmaf(mx8_dequant(pay[o + a], sc[(o + a) >> 5]),
+                   elem_to_f32<K>(row[a]), acc);
+      }
+    }
+    gw[s] = acc;
   }
 }
 
@@ -1476,7 +1787,163 @@ void launch_dequantize_combine_t(const u8* pay, const u8* sc,
   }
 }
 
+template <int K>
+void launch_dequantize_combine_weighted_t(const u8* pay, const u8* sc,
+                                          const long long* src,
+                                          const float* wsrc, void* out,
+                                          int64_t out_slices, int fan,
+                                          int64_t after, hipStream_t stream) {
+  constexpr int EPL = kEPL<K>;
+  // the conditions of launch_dequantize_combine_t
+  if (after % EPL == 0 && aligned(out, 16) && aligned(pay, EPL)) {
+    const long long cps = after / EPL;
+    const long long chunks = out_slices * cps;
+    by_width(chunks, [&](auto i) {
+      using I = decltype(i);
+      hipLaunchKernelGGL((mx8_dequantize_combine_weighted_kernel<K, I>),
+                         dim3(grid_for(chunks)), dim3(256), 0, stream, pay, sc,
+                         src, wsrc, out, (I)chunks, (I)cps, fan);
+    });
+  } else {
+    const long long total = out_slices * after;
+    hipLaunchKernelGGL((mx8_dequantize_combine_weighted_kernel_scalar<K>),
+                       dim3(grid_for(total)), dim3(256), 0, stream, pay, sc,
+                       src, wsrc, out, total, (long long)after, fan);
+  }
+}
+
+// launch_segments_t's quantizing side for rows == 1 with weights; no flat
+// stream shortcut, the flat kernel takes no weights.
+template <int K>
+void launch_quantize_segments_weighted_t(const void* in, const long long* idx,
+                                         const float* wt, u8* pay, u8* sc,
+                                         const Mx8SegDesc* segs, int nsegs,
+                                         int64_t S, int64_t after,
+                                         hipStream_t stream) {
+  constexpr int LPG = kLPG<K>;
+  constexpr int EPL = kEPL<K>;
+  const bool al = aligned(in, 16) && aligned(pay, 32 / LPG);
+  for (int s0 = 0; s0 < nsegs; s0 += kMaxMx8SegsPerLaunch) {
+    const int n = nsegs - s0 < kMaxMx8SegsPerLaunch ? nsegs - s0
+                                                    : kMaxMx8SegsPerLaunch;
+    const SegBatch b = seg_batch(segs + s0, n);
+    if (b.max_count == 0) continue;
+    if (al && after % EPL == 0) {
+      const long long cps = after / EPL;
+      const long long work = (b.max_count * cps + LPG - 1) / LPG * LPG;
+      by_width(work, [&](auto i) {
+        using I = decltype(i);
+        auto go = [&](auto mode) {
+          hipLaunchKernelGGL(
+              (mx8_quantize_segments_weighted_kernel<K, I,
+                                                     decltype(mode)::value>),
+              grid2d(work, n), dim3(256), 0, stream, in, idx, wt, pay, sc,
+              b.args, (long long)S, (I)cps);
+        };
+        if (idx == nullptr) {
+          go(Tag<0>{});
+        } else {
+          go(Tag<1>{});
+        }
+      });
+    } else {
+      const long long G = (b.max_count * after + 31) / 32;
+      auto twin = [&](auto indexed) {
+        constexpr bool IDX = decltype(indexed)::value;
+        hipLaunchKernelGGL(
+            (mx8_quantize_segments_weighted_kernel_scalar<K, IDX>),
+            grid2d(G, n), dim3(256), 0, stream, in, idx, wt, pay, sc, b.args,
+            (long long)S, (long long)after);
+      };
+      if (idx == nullptr) {
+        twin(std::false_type{});
+      } else {
+        twin(std::true_type{});
+      }
+    }
+  }
+}
+
+template <int K>
+void launch_dequantize_rowdot_t(const u8* pay, const u8* sc,
+                                const long long* base, const long long* idx,
+                                const void* g, float* gw, int64_t R,
+                                int64_t out_slices, int64_t after,
+                                hipStream_t stream) {
+  constexpr int EPL = kEPL<K>;
+  if (after % EPL == 0 && aligned(g, 16) && aligned(pay, EPL)) {
+    const long long cps = after / EPL;
+    // the widest per-lane index: a chunk of g, or a slice's padded sweep
+    const long long most = (R > out_slices ? R : out_slices) * cps + 128;
+    by_width(most, [&](auto i) {
+      using I = decltype(i);
+      auto go = [&](auto lps) {
+        constexpr int LPS = decltype(lps)::value;
+        hipLaunchKernelGGL((mx8_dequantize_rowdot_kernel<K, LPS, I>),
+                           dim3(grid_for(R * LPS)), dim3(256), 0, stream, pay,
+                           sc, base, idx, g, gw, (I)R, (I)cps,
+                           (long long)out_slices);
+      };
+      if (cps <= 8) {
+        go(Tag<8>{});
+      } else if (cps <= 16) {
+        go(Tag<16>{});
+      } else if (cps <= 32) {
+        go(Tag<32>{});
+      } else {
+        go(Tag<64>{});
+      }
+    });
+  } else {
+    hipLaunchKernelGGL((mx8_dequantize_rowdot_kernel_scalar<K>),
+                       dim3(grid_for(R)), dim3(256), 0, stream, pay, sc, base,
+                       idx, g, gw, (long long)R, (long long)after,
+                       (long long)out_slices);
+  }
+}
+
 } // namespace
+
+void launch_mx8_dequantize_combine_weighted(
+    const void* payload, const void* scales, const int64_t* src,
+    const float* wsrc, void* out, int64_t out_slices, int fan, int64_t after,
+    int dtype, hipStream_t stream) {
+  if (out_slices <= 0 || after <= 0 || fan <= 0) return;
+  by_dtype(dtype, [&](auto k) {
+    launch_dequantize_combine_weighted_t<k>(
+        static_cast<const u8*>(payload), static_cast<const u8*>(scales),
+        reinterpret_cast<const long long*>(src), wsrc, out, out_slices, fan,
+        after, stream);
+  });
+}
+
+void launch_mx8_quantize_segments_weighted(
+    const void* in, const int64_t* idx, const float* weights, void* payload,
+    void* scales, const Mx8SegDesc* segs, int nsegs, int64_t S, int64_t after,
+    int dtype, hipStream_t stream) {
+  if (nsegs <= 0 || S <= 0 || after <= 0) return;
+  by_dtype(dtype, [&](auto k) {
+    launch_quantize_segments_weighted_t<k>(
+        in, reinterpret_cast<const long long*>(idx), weights,
+        static_cast<u8*>(payload), static_cast<u8*>(scales), segs, nsegs, S,
+        after, stream);
+  });
+}
+
+void launch_mx8_dequantize_rowdot(const void* payload, const void* scales,
+                                  const int64_t* base, const int64_t* idx,
+                                  const void* g, float* gw, int64_t R,
+                                  int64_t out_slices, int64_t after, int dtype,
+                                  hipStream_t stream) {
+  if (R <= 0 || after <= 0) return;
+  by_dtype(dtype, [&](auto k) {
+    launch_dequantize_rowdot_t<k>(
+        static_cast<const u8*>(payload), static_cast<const u8*>(scales),
+        reinterpret_cast<const long long*>(base),
+        reinterpret_cast<const long long*>(idx), g, gw, R, out_slices, after,
+        stream);
+  });
+}
 
 void launch_mx8_dequantize_combine(const void* payload, const void* scales,
                                    const int64_t* src, void* out,

@@ -1342,11 +1342,13 @@ Tensor mx8_alltoall_pairwise(Transport& tr, const Tensor& in, int64_t rows,
 // dropped: they are written to one spare dump slot at the end of the
 // allocation, so nothing out of contract forms an address outside it.
 // Returns the flat allocation [out_size*fan + 1]; the table is its head.
-Tensor mx8_combine_table(const Tensor& index, const Tensor& base,
-                         int64_t out_size, int64_t fan) {
+//
+// mx8_combine_slots is the slot computation alone: (slot, perm) such that
+// source perm[j] belongs at flat table position slot[j] (the dump slot
+// out_size*fan for a dropped one). R must be > 0.
+std::pair<Tensor, Tensor> mx8_combine_slots(const Tensor& index,
+                                            int64_t out_size, int64_t fan) {
   const int64_t R = index.numel();
-  auto table = at::full({out_size * fan + 1}, -1, index.options());
-  if (R == 0) return table;
   auto valid = index.ge(0).logical_and(index.lt(out_size));
   // out-of-range entries sort behind every destination
   auto key = at::where(valid, index, at::full_like(index, out_size));
@@ -1359,24 +1361,53 @@ Tensor mx8_combine_table(const Tensor& index, const Tensor& base,
   auto keep = dest.lt(out_size).logical_and(rank.lt(fan));
   auto slot = at::where(keep, dest * fan + rank,
                         at::full_like(dest, out_size * fan));
-  table.scatter_(0, slot, base.index_select(0, perm));
+  return {slot, perm};
+}
+
+Tensor mx8_combine_table(const Tensor& index, const Tensor& base,
+                         int64_t out_size, int64_t fan) {
+  auto table = at::full({out_size * fan + 1}, -1, index.options());
+  if (index.numel() == 0) return table;
+  const auto sp = mx8_combine_slots(index, out_size, fan);
+  table.scatter_(0, sp.first, base.index_select(0, sp.second));
   return table;
+}
+
+// The offset table and, parallel to it, the fp32 weight table of the weighted
+// tail (weights: fp32 [R]; 0 where the offset table has -1) from one slot
+// computation: no sync, nothing uploaded.
+std::pair<Tensor, Tensor> mx8_combine_tables_weighted(
+    const Tensor& index, const Tensor& base, const Tensor& weights,
+    int64_t out_size, int64_t fan) {
+  auto table = at::full({out_size * fan + 1}, -1, index.options());
+  auto wtab = at::zeros({out_size * fan + 1}, weights.options());
+  if (index.numel() == 0) return {table, wtab};
+  const auto sp = mx8_combine_slots(index, out_size, fan);
+  table.scatter_(0, sp.first, base.index_select(0, sp.second));
+  wtab.scatter_(0, sp.first, weights.index_select(0, sp.second));
+  return {table, wtab};
 }
 
 // The kernel's table: every source entered as the payload byte offset of its
 // slice, 32*goff_p + c*after for slice c of segment p. The offsets are one
 // arange per non-empty segment: the segment plan lives on the host and
 // nothing is uploaded.
-Tensor mx8_combine_offsets_table(const Tensor& index, const Mx8SegPlan& pl,
-                                 int64_t after, int64_t out_size,
-                                 int64_t fan) {
-  auto base = at::empty({pl.slices}, index.options());
+Tensor mx8_slice_offsets(const Mx8SegPlan& pl, int64_t after,
+                         const at::TensorOptions& iopts) {
+  auto base = at::empty({pl.slices}, iopts);
   for (const auto& s : pl.segs) {
     if (s.count == 0) continue;
     auto part = base.narrow(0, s.displ, s.count);
     at::arange_out(part, 32 * s.goff, 32 * s.goff + s.count * after, after);
   }
-  return mx8_combine_table(index, base, out_size, fan);
+  return base;
+}
+
+Tensor mx8_combine_offsets_table(const Tensor& index, const Mx8SegPlan& pl,
+                                 int64_t after, int64_t out_size,
+                                 int64_t fan) {
+  return mx8_combine_table(index, mx8_slice_offsets(pl, after, index.options()),
+                           out_size, fan);
 }
 
 // The rule above on values v [R, after] fp32 through a table [out_size, fan]
@@ -1392,6 +1423,25 @@ Tensor ordered_table_sum(const Tensor& v, const Tensor& tab) {
     acc = at::where(ok, j == 0 ? term : acc + term, acc);
   }
   return acc;
+}
+
+// The received slices of rows == 1 segments as values: fp32 [R, after].
+Tensor mx8_segment_values(const Tensor& pay, const Tensor& sc,
+                          const Mx8SegPlan& pl, int64_t after) {
+  std::vector<Tensor> parts;
+  for (size_t p = 0; p < pl.segs.size(); ++p) {
+    if (pl.groups[p] == 0) continue;
+    const int64_t G = pl.groups[p];
+    parts.push_back(
+        mx8_dequantize_groups(
+            pay.narrow(0, pl.segs[p].goff * 32, G * 32).view({G, 32}),
+            sc.narrow(0, pl.segs[p].goff, G))
+            .view({-1})
+            .narrow(0, 0, pl.segs[p].count * after));
+  }
+  return parts.empty()
+             ? at::zeros({0, after}, pay.options().dtype(at::kFloat))
+             : at::cat(parts).view({pl.slices, after});
 }
 
 // The top-k tail of the pairwise all-to-all (rows == 1): the received
@@ -1421,19 +1471,7 @@ Tensor mx8_dequantize_combine(const Tensor& pay, const Tensor& sc,
                                   current_gpu_stream(pay));
     return out;
   }
-  std::vector<Tensor> parts;
-  for (size_t p = 0; p < counts.size(); ++p) {
-    if (pl.groups[p] == 0) continue;
-    const int64_t G = pl.groups[p];
-    parts.push_back(
-        mx8_dequantize_groups(
-            pay.narrow(0, pl.segs[p].goff * 32, G * 32).view({G, 32}),
-            sc.narrow(0, pl.segs[p].goff, G))
-            .view({-1})
-            .narrow(0, 0, counts[p] * after));
-  }
-  auto v = parts.empty() ? at::zeros({0, after}, pay.options().dtype(at::kFloat))
-                         : at::cat(parts).view({pl.slices, after});
+  auto v = mx8_segment_values(pay, sc, pl, after);
   auto table = mx8_combine_table(index, at::arange(pl.slices, iopts), out_size,
                                  fan);
   auto res = ordered_table_sum(
@@ -1466,6 +1504,179 @@ Tensor mx8_alltoall_pairwise_indexed(
   }
   return mx8_dequantize_combine(stg_pay, stg_sc, after, recv_counts,
                                 *recv_index, out_size, fan, in.scalar_type());
+}
+
+// ---- the gated top-k tail: weights on either side of the wire --------------
+//
+// Rule of the weighted sum (normative; mx8_dequantize_combine_weighted_kernel
+// matches it bit for bit): with w [R] fp32 next to the values,
+//   acc = fl(w * v)(tab[s][0]), or +0.0 when that entry is -1;
+//   acc = acc + fl(w * v)(tab[s][j]) for j = 1..fan-1, -1 skipped;
+// the product rounded to fp32 before the add (two torch ops, no FMA).
+Tensor weighted_table_sum(const Tensor& v, const Tensor& w,
+                          const Tensor& tab) {
+  const int64_t out_size = tab.size(0), fan = tab.size(1);
+  auto acc = at::zeros({out_size, v.size(1)}, v.options());
+  if (v.size(0) == 0) return acc;
+  for (int64_t j = 0; j < fan; ++j) {
+    auto col = tab.select(1, j);
+    auto ok = col.ge(0).unsqueeze(1);
+    auto src = col.clamp_min(0);
+    auto term = w.index_select(0, src).unsqueeze(1) * v.index_select(0, src);
+    acc = at::where(ok, j == 0 ? term : acc + term, acc);
+  }
+  return acc;
+}
+
+Tensor table_view(const Tensor& flat, int64_t out_size, int64_t fan) {
+  return flat.narrow(0, 0, out_size * fan).view({out_size, fan});
+}
+
+// mx8_dequantize_combine with weights (fp32 [R], one per received slice).
+Tensor mx8_dequantize_combine_weighted(
+    const Tensor& pay, const Tensor& sc, int64_t after,
+    const std::vector<int64_t>& counts, const Tensor& index,
+    const Tensor& weights, int64_t out_size, int64_t fan,
+    at::ScalarType dtype, const c10::optional<Tensor>& out_opt = c10::nullopt) {
+  const int dt = mx8_dtype_code(dtype);
+  const auto pl = mx8_seg_plan(counts, 1, after);
+  if (pay.is_cuda()) {
+    auto out = out_or_empty(out_opt, {out_size, after},
+                            pay.options().dtype(dtype));
+    auto tabs = mx8_combine_tables_weighted(
+        index, mx8_slice_offsets(pl, after, index.options()), weights,
+        out_size, fan);
+    launch_mx8_dequantize_combine_weighted(
+        pay.data_ptr(), sc.data_ptr(), tabs.first.data_ptr<int64_t>(),
+        tabs.second.data_ptr<float>(), out.data_ptr(), out_size, (int)fan,
+        after, dt, current_gpu_stream(pay));
+    return out;
+  }
+  auto table = mx8_combine_table(index, at::arange(pl.slices, index.options()),
+                                 out_size, fan);
+  auto res = weighted_table_sum(mx8_segment_values(pay, sc, pl, after),
+                                weights, table_view(table, out_size, fan))
+                 .to(dtype);
+  return out_opt.has_value() ? out_opt->copy_(res) : res;
+}
+
+// mx8_quantize_segments for rows == 1 with weights (fp32 [sum(counts)]):
+// stream slice i is fl32(w_i * f32(in[order_i])) (in[i] without an order),
+// an order entry outside [0, S) reading as zeros; segment p is mx8_quantize
+// of its fp32 products. The product never rounds to in's dtype.
+std::pair<Tensor, Tensor> mx8_quantize_segments_weighted(
+    const Tensor& in, int64_t after, const std::vector<int64_t>& counts,
+    const c10::optional<Tensor>& order, const Tensor& weights,
+    const c10::optional<Tensor>& payload_out = c10::nullopt,
+    const c10::optional<Tensor>& scales_out = c10::nullopt) {
+  const int dt = mx8_dtype_code(in.scalar_type());
+  const auto pl = mx8_seg_plan(counts, 1, after);
+  const int64_t S = after > 0 ? in.numel() / after : 0;
+  auto bopts = in.options().dtype(at::kByte);
+  auto pay = payload_out.has_value()
+                 ? payload_out->narrow(0, 0, pl.total_groups * 32)
+                 : at::empty({pl.total_groups * 32}, bopts);
+  auto sc = scales_out.has_value() ? scales_out->narrow(0, 0, pl.total_groups)
+                                   : at::empty({pl.total_groups}, bopts);
+  if (pl.total_groups == 0) return {pay, sc};
+  if (in.is_cuda()) {
+    launch_mx8_quantize_segments_weighted(
+        in.data_ptr(),
+        order.has_value() ? order->data_ptr<int64_t>() : nullptr,
+        weights.data_ptr<float>(), pay.data_ptr(), sc.data_ptr(),
+        pl.segs.data(), (int)pl.segs.size(), S, after, dt,
+        current_gpu_stream(in));
+    return {pay, sc};
+  }
+  auto xs = in.view({S, after}).to(at::kFloat);
+  if (order.has_value()) {
+    auto ok = order->ge(0).logical_and(order->lt(S)).unsqueeze(1);
+    xs = at::where(ok, xs.index_select(0, order->clamp(0, S > 0 ? S - 1 : 0)),
+                   at::zeros({}, xs.options()));
+  }
+  auto prod = weights.unsqueeze(1) * xs;
+  for (size_t p = 0; p < counts.size(); ++p) {
+    if (pl.groups[p] == 0) continue;
+    auto q = mx8_quantize(
+        prod.narrow(0, pl.segs[p].displ, counts[p]).contiguous().view({-1}));
+    pay.narrow(0, pl.segs[p].goff * 32, pl.groups[p] * 32).copy_(q.first);
+    sc.narrow(0, pl.segs[p].goff, pl.groups[p]).copy_(q.second);
+  }
+  return {pay, sc};
+}
+
+// The gate gradient of the gated tail: gw[i] = sum_a dq(received slice i)[a] *
+// f32(g[index[i]][a]) in fp32 [R]; g is contiguous [out_size, after]. 0 for
+// an index outside [0, out_size). The kernel owns its order of association,
+// so it agrees with this composite to fp32 summation rounding, not bit for
+// bit.
+Tensor mx8_dequantize_rowdot(const Tensor& pay, const Tensor& sc,
+                             int64_t after,
+                             const std::vector<int64_t>& counts,
+                             const Tensor& index, const Tensor& g,
+                             const c10::optional<Tensor>& out_opt =
+                                 c10::nullopt) {
+  const int dt = mx8_dtype_code(g.scalar_type());
+  const auto pl = mx8_seg_plan(counts, 1, after);
+  const int64_t out_size = g.size(0);
+  auto fopts = pay.options().dtype(at::kFloat);
+  if (pay.is_cuda()) {
+    auto out = out_or_empty(out_opt, {pl.slices}, fopts);
+    auto base = mx8_slice_offsets(pl, after, index.options());
+    launch_mx8_dequantize_rowdot(
+        pay.data_ptr(), sc.data_ptr(), base.data_ptr<int64_t>(),
+        index.data_ptr<int64_t>(), g.data_ptr(), out.data_ptr<float>(),
+        pl.slices, out_size, after, dt, current_gpu_stream(pay));
+    return out;
+  }
+  Tensor res = at::zeros({pl.slices}, fopts);
+  if (pl.slices > 0 && out_size > 0) {
+    auto ok = index.ge(0).logical_and(index.lt(out_size));
+    auto rows = g.index_select(0, index.clamp(0, out_size - 1)).to(at::kFloat);
+    res = at::where(ok, (mx8_segment_values(pay, sc, pl, after) * rows).sum(1),
+                    res);
+  }
+  return out_opt.has_value() ? out_opt->copy_(res) : res;
+}
+
+// mx8_alltoall_pairwise_indexed for rows == 1 with weights on either side:
+// the head scales stream slice i by send_weights[i] before it quantizes, the
+// tail scales received slice i by recv_weights[i] while it sums (recv_weights
+// needs recv_index). With `wire` the received payload and scale bytes are
+// handed out as well: the gate gradient is computed from them.
+Tensor mx8_alltoall_pairwise_weighted(
+    Transport& tr, const Tensor& in, int64_t after,
+    const std::vector<int64_t>& send_counts,
+    const std::vector<int64_t>& recv_counts,
+    const c10::optional<Tensor>& send_index,
+    const c10::optional<Tensor>& send_weights,
+    const c10::optional<Tensor>& recv_index,
+    const c10::optional<Tensor>& recv_weights, int64_t out_size, int64_t fan,
+    std::pair<Tensor, Tensor>* wire) {
+  const auto sp = mx8_seg_plan(send_counts, 1, after);
+  const auto rp = mx8_seg_plan(recv_counts, 1, after);
+  auto q = send_weights.has_value()
+               ? mx8_quantize_segments_weighted(in, after, send_counts,
+                                                send_index, *send_weights)
+               : mx8_quantize_segments(in, 1, after, send_counts, send_index);
+  auto bopts = in.options().dtype(at::kByte);
+  auto stg_pay = at::empty({rp.total_groups * 32}, bopts);
+  auto stg_sc = at::empty({rp.total_groups}, bopts);
+  mx8_exchange(tr, {q.first, q.second, sp.goffs(), sp.groups},
+               {stg_pay, stg_sc, rp.goffs(), rp.groups});
+  if (wire != nullptr) *wire = {stg_pay, stg_sc};
+  if (!recv_index.has_value()) {
+    return mx8_dequantize_segments(stg_pay, stg_sc, 1, after, recv_counts,
+                                   c10::nullopt, in.scalar_type());
+  }
+  if (!recv_weights.has_value()) {
+    return mx8_dequantize_combine(stg_pay, stg_sc, after, recv_counts,
+                                  *recv_index, out_size, fan,
+                                  in.scalar_type());
+  }
+  return mx8_dequantize_combine_weighted(stg_pay, stg_sc, after, recv_counts,
+                                         *recv_index, *recv_weights, out_size,
+                                         fan, in.scalar_type());
 }
 
 // The mxfp8 sibling of hierarchical_allreduce: quantize once, exchange each
@@ -3153,30 +3364,59 @@ struct AlltoallPairwiseCompressedIndexedBackward : public M4ANode {
 // Shape, dtype and device always; range and the repeat bound on the CPU,
 // and on the GPU only under the desync detector's debug mode (they cost a
 // sync).
-void check_pairwise_index(const char* which,
+void check_pairwise_index(const char* who, const char* which,
                           const c10::optional<Tensor>& index, int64_t len,
                           int64_t size, int64_t max_repeat,
                           const Tensor& input) {
   if (!index.has_value()) return;
   const Tensor& o = *index;
   TORCH_CHECK(o.dim() == 1 && o.numel() == len,
-              "AlltoallPairwiseCompressedIndexed: ", which, " must be a 1-D "
+              who, ": ", which, " must be a 1-D "
               "tensor of length ", len, " (the sum of its counts), got shape ",
               o.sizes());
   TORCH_CHECK(o.scalar_type() == at::kLong,
-              "AlltoallPairwiseCompressedIndexed: ", which, " must be an "
+              who, ": ", which, " must be an "
               "int64 tensor, got ", o.scalar_type());
   TORCH_CHECK(o.device() == input.device(),
-              "AlltoallPairwiseCompressedIndexed: ", which, " must be on the "
+              who, ": ", which, " must be on the "
               "tensor's device ", input.device(), ", got ", o.device());
   if (len > 0 && (!o.is_cuda() || config().debug_collectives)) {
     TORCH_CHECK(o.min().item<int64_t>() >= 0 && o.max().item<int64_t>() < size,
-                "AlltoallPairwiseCompressedIndexed: ", which, " entries must "
+                who, ": ", which, " entries must "
                 "lie in [0, ", size, ")");
     const int64_t most = at::bincount(o).max().item<int64_t>();
     TORCH_CHECK(most <= max_repeat,
-                "AlltoallPairwiseCompressedIndexed: a slice occurs ", most,
+                who, ": a slice occurs ", most,
                 " times in ", which, ", more than max_repeat = ", max_repeat);
+  }
+}
+
+// The counts of a pairwise exchange: recv_counts exchanged when empty (my
+// recv from j = j's send to me), both checked, their sums returned.
+void resolve_pairwise_counts(const char* who, Transport& tr0,
+                             const std::string& group_name,
+                             std::vector<int64_t>& send_counts,
+                             std::vector<int64_t>& recv_counts,
+                             int64_t* s_total, int64_t* r_total) {
+  const int P = tr0.size();
+  TORCH_CHECK((int)send_counts.size() == P, who,
+              ": send_counts must have world_size entries");
+  if (recv_counts.empty() && P > 1) {
+    auto mat = host_allgather_int64_vec(group_name, send_counts);
+    recv_counts.resize(P);
+    const int me = tr0.rank();
+    for (int j = 0; j < P; ++j) recv_counts[j] = mat[(int64_t)j * P + me];
+  }
+  if (P == 1 && recv_counts.empty()) recv_counts = send_counts;
+  TORCH_CHECK((int)recv_counts.size() == P, who,
+              ": recv_counts must have world_size entries");
+  for (int64_t c : send_counts) {
+    TORCH_CHECK(c >= 0, who, ": negative send count ", c);
+    *s_total += c;
+  }
+  for (int64_t c : recv_counts) {
+    TORCH_CHECK(c >= 0, who, ": negative recv count ", c);
+    *r_total += c;
   }
 }
 } // namespace
@@ -3189,29 +3429,9 @@ Tensor Communicator::AlltoallPairwiseCompressedIndexed(
   const char* who = "AlltoallPairwiseCompressedIndexed";
   check_mx8_input(who, input);
   axis = at::maybe_wrap_dim(axis, input.dim());
-  auto& tr0 = cpu_tr();
-  const int P = tr0.size();
-  TORCH_CHECK((int)send_counts.size() == P, who,
-              ": send_counts must have world_size entries");
-  if (recv_counts.empty() && P > 1) {
-    // exchange the count matrix; my recv from j = j's send to me
-    auto mat = host_allgather_int64_vec(group_name_, send_counts);
-    recv_counts.resize(P);
-    const int me = tr0.rank();
-    for (int j = 0; j < P; ++j) recv_counts[j] = mat[(int64_t)j * P + me];
-  }
-  if (P == 1 && recv_counts.empty()) recv_counts = send_counts;
-  TORCH_CHECK((int)recv_counts.size() == P, who,
-              ": recv_counts must have world_size entries");
   int64_t s_total = 0, r_total = 0;
-  for (int64_t c : send_counts) {
-    TORCH_CHECK(c >= 0, who, ": negative send count ", c);
-    s_total += c;
-  }
-  for (int64_t c : recv_counts) {
-    TORCH_CHECK(c >= 0, who, ": negative recv count ", c);
-    r_total += c;
-  }
+  resolve_pairwise_counts(who, cpu_tr(), group_name_, send_counts, recv_counts,
+                          &s_total, &r_total);
   TORCH_CHECK(max_repeat >= 1, who, ": max_repeat must be >= 1, got ",
               max_repeat);
   const int64_t in_size = input.size(axis);
@@ -3228,10 +3448,10 @@ Tensor Communicator::AlltoallPairwiseCompressedIndexed(
               "size 1 (token tensors are [N, D]), got shape ", input.sizes(),
               " with axis ", axis);
   const int64_t n_out = recv_index.has_value() ? *out_size : r_total;
-  check_pairwise_index("send_index", send_index, s_total, in_size, max_repeat,
-                       input);
-  check_pairwise_index("recv_index", recv_index, r_total, n_out, max_repeat,
-                       input);
+  check_pairwise_index(who, "send_index", send_index, s_total, in_size,
+                       max_repeat, input);
+  check_pairwise_index(who, "recv_index", recv_index, r_total, n_out,
+                       max_repeat, input);
 
   auto make_grad_fn = [&](auto comm) {
     return make_node<AlltoallPairwiseCompressedIndexedBackward>(
@@ -3274,6 +3494,230 @@ Tensor Communicator::AlltoallPairwiseCompressedIndexed(
         .view(outsizes);
   };
   return collective_frame(*this, input, make_grad_fn, body);
+}
+
+// ---------------------------------------------------------------------------
+// AlltoallPairwiseCompressedWeighted (MI355X extension; not in the reference
+// API): AlltoallPairwiseCompressedIndexed with one weight per stream slice
+// on either side. The receive weights are the gates of a top-k MoE combine,
+// applied in fp32 on the token's home rank while the kernel sums; they are
+// differentiable, their gradient a fused row dot on the wire bytes the
+// forward received. The send weights exist to be the adjoint.
+// ---------------------------------------------------------------------------
+
+namespace {
+struct AlltoallPairwiseCompressedWeightedBackward : public M4ANode {
+  std::string name() const override {
+    return "M4AAlltoallPairwiseCompressedWeightedBackward";
+  }
+  void release_variables() override {
+    wire_pay.reset();
+    wire_sc.reset();
+    values.reset();
+  }
+  variable_list apply(variable_list&& grads) override {
+    variable_list out(2);
+    const Tensor& g = grads[0];
+    if (should_compute_output(0)) {
+      // the adjoint: counts, indices and weights swap sides; a send weight
+      // on an identity send needs the identity spelled out as a recv index
+      auto ri = send_index;
+      if (send_weights.has_value() && !ri.has_value()) {
+        ri = at::arange(in_size, g.options().dtype(at::kLong));
+      }
+      out[0] = comm->AlltoallPairwiseCompressedWeighted(
+          g, axis, recv, send, recv_index, recv_weights, ri, send_weights,
+          ri.has_value() ? c10::optional<int64_t>(in_size) : c10::nullopt,
+          max_repeat);
+    }
+    if (should_compute_output(1)) {
+      at::AutoDispatchBelowADInplaceOrView guard;
+      TORCH_CHECK(wire_pay.defined() || values.defined(),
+                  "AlltoallPairwiseCompressedWeighted: backward through the "
+                  "weights a second time, after the saved wire bytes were "
+                  "freed");
+      DeviceStager stager(g);
+      auto gc = stager.to_comm(g).contiguous().variable_data()
+                    .view({out_size, after});
+      Tensor gw;
+      if (values.defined()) {
+        // world of one: the dot on the values themselves
+        gw = at::zeros({values.size(0)}, gc.options().dtype(at::kFloat));
+        if (values.size(0) > 0 && out_size > 0) {
+          const Tensor& t = *recv_index_comm;
+          auto ok = t.ge(0).logical_and(t.lt(out_size));
+          auto rows = gc.index_select(0, t.clamp(0, out_size - 1));
+          gw = at::where(
+              ok, (values.to(at::kFloat) * rows.to(at::kFloat)).sum(1), gw);
+        }
+      } else {
+        gw = mx8_dequantize_rowdot(wire_pay, wire_sc, after, recv,
+                                   *recv_index_comm, gc);
+      }
+      out[1] = stager.from_comm(gw).to(weight_dtype);
+    }
+    return out;
+  }
+  int64_t axis = 0, in_size = 0, out_size = 0, after = 0, max_repeat = 1;
+  // as the forward had them (the weights detached); recv_index a second
+  // time where the wire bytes live
+  std::vector<int64_t> send, recv;
+  c10::optional<Tensor> send_index, recv_index, send_weights, recv_weights;
+  c10::optional<Tensor> recv_index_comm;
+  at::ScalarType weight_dtype = at::kFloat;
+  Tensor wire_pay, wire_sc;  // what the forward received, 33/32 byte/element
+  Tensor values;             // world of one: the [R, after] values instead
+};
+
+// 1-D, length, dtype (fp32 or the input's) and device of a weight tensor.
+void check_pairwise_weights(const char* who, const char* which,
+                            const c10::optional<Tensor>& w, int64_t len,
+                            const Tensor& input) {
+  if (!w.has_value()) return;
+  TORCH_CHECK(w->dim() == 1 && w->numel() == len, who, ": ", which,
+              " must be a 1-D tensor of length ", len,
+              " (the sum of its counts), got shape ", w->sizes());
+  TORCH_CHECK(w->scalar_type() == at::kFloat ||
+                  w->scalar_type() == input.scalar_type(),
+              who, ": ", which, " must be float32 or the tensor's dtype ",
+              input.scalar_type(), ", got ", w->scalar_type());
+  TORCH_CHECK(w->device() == input.device(), who, ": ", which,
+              " must be on the tensor's device ", input.device(), ", got ",
+              w->device());
+}
+} // namespace
+
+Tensor Communicator::AlltoallPairwiseCompressedWeighted(
+    const Tensor& input, int64_t axis, std::vector<int64_t> send_counts,
+    std::vector<int64_t> recv_counts, c10::optional<Tensor> send_index,
+    c10::optional<Tensor> send_weights, c10::optional<Tensor> recv_index,
+    c10::optional<Tensor> recv_weights, c10::optional<int64_t> out_size,
+    int64_t max_repeat) {
+  const char* who = "AlltoallPairwiseCompressedWeighted";
+  if (!send_weights.has_value() && !recv_weights.has_value()) {
+    return AlltoallPairwiseCompressedIndexed(
+        input, axis, std::move(send_counts), std::move(recv_counts),
+        std::move(send_index), std::move(recv_index), out_size, max_repeat);
+  }
+  check_mx8_input(who, input);
+  axis = at::maybe_wrap_dim(axis, input.dim());
+  TORCH_CHECK(!recv_weights.has_value() || recv_index.has_value(), who,
+              ": recv_weights need a recv_index");
+  TORCH_CHECK(!send_weights.has_value() || !send_weights->requires_grad(), who,
+              ": send_weights are not differentiable (they exist to be the "
+              "adjoint of recv_weights); detach them");
+  int64_t s_total = 0, r_total = 0;
+  resolve_pairwise_counts(who, cpu_tr(), group_name_, send_counts, recv_counts,
+                          &s_total, &r_total);
+  TORCH_CHECK(max_repeat >= 1, who, ": max_repeat must be >= 1, got ",
+              max_repeat);
+  const int64_t in_size = input.size(axis);
+  TORCH_CHECK(send_index.has_value() || in_size == s_total, who,
+              ": without a send_index the sum of send_counts (", s_total,
+              ") must equal the axis size (", in_size, ")");
+  TORCH_CHECK(!recv_index.has_value() || out_size.has_value(), who,
+              ": out_size is required with a recv_index");
+  TORCH_CHECK(!out_size.has_value() || *out_size >= 0, who,
+              ": out_size must be >= 0, got ", out_size.value_or(0));
+  const auto g0 = axis_geom(input, axis);
+  TORCH_CHECK(g0.before == 1, who,
+              ": with weights every dimension before the axis must have size "
+              "1 (token tensors are [N, D]), got shape ", input.sizes(),
+              " with axis ", axis);
+  const int64_t n_out = recv_index.has_value() ? *out_size : r_total;
+  check_pairwise_index(who, "send_index", send_index, s_total, in_size,
+                       max_repeat, input);
+  check_pairwise_index(who, "recv_index", recv_index, r_total, n_out,
+                       max_repeat, input);
+  check_pairwise_weights(who, "send_weights", send_weights, s_total, input);
+  check_pairwise_weights(who, "recv_weights", recv_weights, r_total, input);
+
+  // collective_frame written out: two differentiable inputs, and the node
+  // receives what the body saves for it
+  const Tensor rw_in = recv_weights.value_or(Tensor());
+  std::shared_ptr<AlltoallPairwiseCompressedWeightedBackward> node;
+  if (torch::autograd::compute_requires_grad(input, rw_in)) {
+    node = make_node<AlltoallPairwiseCompressedWeightedBackward>(
+        c10::intrusive_ptr<Communicator>::unsafe_reclaim_from_nonowning(this));
+    node->set_next_edges(torch::autograd::collect_next_edges(input, rw_in));
+    node->axis = axis;
+    node->in_size = in_size;
+    node->out_size = n_out;
+    node->after = g0.after;
+    node->max_repeat = max_repeat;
+    node->send = send_counts;
+    node->recv = recv_counts;
+    node->send_index = send_index;
+    node->recv_index = recv_index;
+    if (send_weights.has_value()) node->send_weights = send_weights->detach();
+    if (rw_in.defined()) {
+      node->recv_weights = rw_in.detach();
+      node->weight_dtype = rw_in.scalar_type();
+    }
+  }
+  // the wire bytes are kept only for a weight that wants its gradient
+  const bool need_gw = node && rw_in.requires_grad();
+  auto body = [&](Transport& tr, const Tensor& in,
+                  const DeviceStager& stager) -> Tensor {
+    // index and weight tensors follow the input through the stager; the
+    // weights travel nowhere and are cast to fp32 here
+    auto staged = [&](const c10::optional<Tensor>& t, bool weight) {
+      c10::optional<Tensor> o;
+      if (t.has_value()) {
+        auto c = stager.to_comm(*t).contiguous().variable_data();
+        o = weight ? c.to(at::kFloat) : c;
+      }
+      return o;
+    };
+    const auto si = staged(send_index, false), ri = staged(recv_index, false);
+    const auto sw = staged(send_weights, true), rw = staged(recv_weights, true);
+    if (node) node->recv_index_comm = ri;
+    auto outsizes = in.sizes().vec();
+    outsizes[axis] = n_out;
+    const int64_t after = g0.after;
+    // World of one: the exact, uncompressed result — gather, fp32 weighting,
+    // ordered table sum, cast. force_full_path runs the whole pipeline on
+    // either device.
+    if (w1_shortcut(tr)) {
+      auto y = si.has_value() ? in.index_select(axis, *si) : in;
+      auto yv = y.view({r_total, after});
+      if (sw.has_value()) yv = sw->unsqueeze(1) * yv.to(at::kFloat);
+      // the input's own storage is not kept
+      if (need_gw) node->values = yv.is_alias_of(in) ? yv.clone() : yv;
+      if (!ri.has_value()) return yv.to(in.scalar_type()).view(outsizes);
+      auto table = mx8_combine_table(*ri, at::arange(r_total, ri->options()),
+                                     n_out, max_repeat);
+      auto tab = table_view(table, n_out, max_repeat);
+      auto yf = yv.to(at::kFloat);
+      return (rw.has_value() ? weighted_table_sum(yf, *rw, tab)
+                             : ordered_table_sum(yf, tab))
+          .to(in.scalar_type())
+          .view(outsizes);
+    }
+    debug_check_axis_collective(group_name_, who, in, {axis}, {axis});
+    if (after == 0) {
+      // nothing to send; the weights' gradient is a dot over no elements
+      if (need_gw) node->values = at::zeros({r_total, 0}, in.options());
+      return at::zeros(outsizes, in.options());
+    }
+    std::pair<Tensor, Tensor> wire;
+    auto out = mx8_alltoall_pairwise_weighted(
+        tr, in, after, send_counts, recv_counts, si, sw, ri, rw, n_out,
+        max_repeat, need_gw ? &wire : nullptr);
+    if (need_gw) {
+      node->wire_pay = wire.first;
+      node->wire_sc = wire.second;
+    }
+    return out.view(outsizes);
+  };
+  auto result = [&]() {
+    at::AutoDispatchBelowADInplaceOrView guard;
+    DeviceStager stager(input);
+    auto in = stager.to_comm(input).contiguous().variable_data();
+    return stager.from_comm(body(tr_for(in), in, stager));
+  }();
+  attach_history(result, node);
+  return result;
 }
 
 // ---------------------------------------------------------------------------
@@ -3997,6 +4441,111 @@ Tensor debug_mx8_combine_table(const Tensor& index, int64_t after,
                                    fan)
       .narrow(0, 0, out_size * fan)
       .view({out_size, fan});
+}
+
+namespace {
+// the wire of rows == 1 segments, as the debug bindings take it
+void check_debug_wire(const char* binding, const Tensor& payload,
+                      const Tensor& scales, const Mx8SegPlan& pl) {
+  TORCH_CHECK(payload.dim() == 1 && scales.dim() == 1 &&
+                  payload.is_contiguous() && scales.is_contiguous() &&
+                  payload.scalar_type() == at::kByte &&
+                  scales.scalar_type() == at::kByte &&
+                  payload.numel() == pl.total_groups * 32 &&
+                  scales.numel() == pl.total_groups &&
+                  payload.device() == scales.device(),
+              binding, " expects flat contiguous uint8 payload [32*sum(G)] "
+              "and scales [sum(G)]");
+}
+
+// index (int64) or weights (float32): contiguous, one per slice, on `dev`
+void check_debug_per_slice(const char* binding, const char* which,
+                           const Tensor& t, at::ScalarType dtype, int64_t len,
+                           const at::Device& dev) {
+  TORCH_CHECK(t.dim() == 1 && t.numel() == len && t.scalar_type() == dtype &&
+                  t.is_contiguous() && t.device() == dev,
+              binding, ": ", which, " must be a contiguous ", dtype,
+              " tensor of sum(counts) entries on the data's device");
+}
+} // namespace
+
+Tensor debug_mx8_dequantize_combine_weighted(
+    const Tensor& payload, const Tensor& scales, int64_t after,
+    std::vector<int64_t> counts, const Tensor& index, const Tensor& weights,
+    int64_t out_size, int64_t fan, at::ScalarType dtype,
+    const c10::optional<Tensor>& out) {
+  const char* who = "debug_mx8_dequantize_combine_weighted";
+  TORCH_CHECK(after >= 1 && out_size >= 0 && fan >= 1, who,
+              ": after and fan must be >= 1 and out_size >= 0");
+  const auto pl = mx8_seg_plan(counts, 1, after);
+  check_debug_wire(who, payload, scales, pl);
+  check_debug_per_slice(who, "index", index, at::kLong, pl.slices,
+                        payload.device());
+  check_debug_per_slice(who, "weights", weights, at::kFloat, pl.slices,
+                        payload.device());
+  c10::optional<Tensor> head;
+  if (out.has_value()) {
+    const int64_t total = out_size * after;
+    check_canary_out(who, *out, total, dtype, payload.device(),
+                     "out_size*after");
+    head = out->narrow(0, 0, total).view({out_size, after});
+  }
+  return mx8_dequantize_combine_weighted(payload, scales, after, counts, index,
+                                         weights, out_size, fan, dtype, head);
+}
+
+std::tuple<Tensor, Tensor> debug_mx8_quantize_segments_weighted(
+    const Tensor& x, int64_t after, std::vector<int64_t> counts,
+    const Tensor& weights, const c10::optional<Tensor>& order,
+    const c10::optional<Tensor>& payload_out,
+    const c10::optional<Tensor>& scales_out) {
+  const char* who = "debug_mx8_quantize_segments_weighted";
+  TORCH_CHECK(x.dim() == 1 && x.is_contiguous() && after >= 1 &&
+                  x.numel() % after == 0,
+              who, " expects a flat contiguous tensor of S*after elements");
+  TORCH_CHECK(payload_out.has_value() == scales_out.has_value(), who,
+              ": payload_out and scales_out go together");
+  const auto pl = mx8_seg_plan(counts, 1, after);
+  if (order.has_value()) {
+    check_debug_per_slice(who, "order", *order, at::kLong, pl.slices,
+                          x.device());
+  } else {
+    TORCH_CHECK(pl.slices == x.numel() / after, who,
+                ": sum(counts) must equal the number of slices ",
+                x.numel() / after);
+  }
+  check_debug_per_slice(who, "weights", weights, at::kFloat, pl.slices,
+                        x.device());
+  if (payload_out.has_value()) {
+    check_canary_wire(who, *payload_out, *scales_out, pl.total_groups,
+                      x.device(), "32*sum(G) and sum(G)");
+  }
+  auto ps = mx8_quantize_segments_weighted(x, after, counts, order, weights,
+                                           payload_out, scales_out);
+  return std::make_tuple(ps.first, ps.second);
+}
+
+Tensor debug_mx8_dequantize_rowdot(const Tensor& payload, const Tensor& scales,
+                                   int64_t after, std::vector<int64_t> counts,
+                                   const Tensor& index, const Tensor& g,
+                                   const c10::optional<Tensor>& out) {
+  const char* who = "debug_mx8_dequantize_rowdot";
+  TORCH_CHECK(after >= 1, who, ": after must be >= 1");
+  const auto pl = mx8_seg_plan(counts, 1, after);
+  check_debug_wire(who, payload, scales, pl);
+  check_debug_per_slice(who, "index", index, at::kLong, pl.slices,
+                        payload.device());
+  TORCH_CHECK(g.dim() == 2 && g.size(1) == after && g.is_contiguous() &&
+                  g.device() == payload.device(),
+              who, ": g must be a contiguous [out_size, after] tensor on the "
+              "payload's device");
+  c10::optional<Tensor> head;
+  if (out.has_value()) {
+    check_canary_out(who, *out, pl.slices, at::kFloat, payload.device(),
+                     "sum(counts)");
+    head = out->narrow(0, 0, pl.slices);
+  }
+  return mx8_dequantize_rowdot(payload, scales, after, counts, index, g, head);
 }
 
 Tensor debug_pairloc_reduce(const Tensor& stacked, int64_t op) {

@@ -141,6 +141,27 @@ struct Communicator : torch::CustomClassHolder {
       c10::optional<at::Tensor> recv_index, c10::optional<int64_t> out_size,
       int64_t max_repeat);
 
+  // The above with one weight per stream slice on either side (1-D, on the
+  // tensor's device, float32 or the tensor's dtype; dimensions before the
+  // axis of size 1). send_weights [sum(send_counts)]: stream slice i is
+  // fl32(w_i * f32(slice)), quantized from the products; not differentiable.
+  // recv_weights [sum(recv_counts)] (needs recv_index): out[s] = the fp32 sum
+  // over the received slices i with recv_index[i] == s, in ascending i, of
+  // fl32(w_i * dq(slice i)), product rounded before the add, one cast: the
+  // gate of a top-k MoE applied on the token's home rank inside the combine
+  // kernel. Backward: for the tensor, the same op with counts, indices and
+  // weights swapped; for recv_weights, gw_i = sum_a dq(slice i)[a] *
+  // grad[recv_index[i]][a] by a fused row-dot kernel on the wire bytes the
+  // forward received (kept only when recv_weights requires grad). Without
+  // weights this is AlltoallPairwiseCompressedIndexed.
+  at::Tensor AlltoallPairwiseCompressedWeighted(
+      const at::Tensor& input, int64_t axis, std::vector<int64_t> send_counts,
+      std::vector<int64_t> recv_counts, c10::optional<at::Tensor> send_index,
+      c10::optional<at::Tensor> send_weights,
+      c10::optional<at::Tensor> recv_index,
+      c10::optional<at::Tensor> recv_weights, c10::optional<int64_t> out_size,
+      int64_t max_repeat);
+
   // Non-blocking allreduce (MI355X-first overlap primitive, not in the
   // reference API): returns a wait handle; no autograd through it — use
   // Allreduce for differentiable paths. Gradient bucketing (parallel/ddp)
@@ -270,6 +291,27 @@ at::Tensor debug_mx8_dequantize_combine(
 at::Tensor debug_mx8_combine_table(const at::Tensor& index, int64_t after,
                                    std::vector<int64_t> counts,
                                    int64_t out_size, int64_t fan);
+// the three kernels of AlltoallPairwiseCompressedWeighted (composites for CPU
+// tensors). weights: contiguous float32, one per stream slice.
+// _combine_weighted: debug_mx8_dequantize_combine with fl32(w_i * v_i) terms.
+at::Tensor debug_mx8_dequantize_combine_weighted(
+    const at::Tensor& payload, const at::Tensor& scales, int64_t after,
+    std::vector<int64_t> counts, const at::Tensor& index,
+    const at::Tensor& weights, int64_t out_size, int64_t fan,
+    at::ScalarType dtype, const c10::optional<at::Tensor>& out);
+// _segments_weighted: debug_mx8_quantize_segments for rows == 1, stream slice
+// i = fl32(w_i * f32(x[order_i])), an order entry outside [0, S) as zeros.
+std::tuple<at::Tensor, at::Tensor> debug_mx8_quantize_segments_weighted(
+    const at::Tensor& x, int64_t after, std::vector<int64_t> counts,
+    const at::Tensor& weights, const c10::optional<at::Tensor>& order,
+    const c10::optional<at::Tensor>& payload_out,
+    const c10::optional<at::Tensor>& scales_out);
+// _rowdot: gw [R] float32, gw_i = sum_a dq(slice i)[a] * g[index_i][a] with
+// g [out_size, after] contiguous; 0 for an index outside [0, out_size).
+at::Tensor debug_mx8_dequantize_rowdot(
+    const at::Tensor& payload, const at::Tensor& scales, int64_t after,
+    std::vector<int64_t> counts, const at::Tensor& index, const at::Tensor& g,
+    const c10::optional<at::Tensor>& out);
 // staging: flat P rank-major blocks of [rows, row_elems]; out: contiguous
 // [rows, P, row_elems]. The axis unpack of an equal-count Allgather.
 void debug_unpack_blocks(const at::Tensor& staging, const at::Tensor& out);

@@ -432,6 +432,51 @@ class MPI_Communicator:
             tensor, axis, send_counts, recv_counts, send_index, recv_index,
             out_size, max_repeat)
 
+    def AlltoallPairwiseCompressedWeighted(
+            self, tensor: torch.Tensor, axis: int, send_counts: List[int],
+            recv_counts: List[int],
+            send_index: Optional[torch.Tensor] = None,
+            send_weights: Optional[torch.Tensor] = None,
+            recv_index: Optional[torch.Tensor] = None,
+            recv_weights: Optional[torch.Tensor] = None,
+            out_size: Optional[int] = None,
+            max_repeat: int = 1) -> torch.Tensor:
+        """AlltoallPairwiseCompressedIndexed with one weight per stream
+        slice on either side (MI355X extension): the combine of a top-k
+        mixture-of-experts layer that applies the gates on the token's home
+        rank, inside the kernel that sums.
+
+        Weights are 1-D tensors on the tensor's device, float32 or the
+        tensor's dtype (they are cast to float32), one per slice of their
+        side's stream; with a weight every dimension before ``axis`` must
+        have size 1.
+
+        ``recv_weights`` (length ``sum(recv_counts)``, needs ``recv_index``):
+        ``out[s]`` is the sum over the received slices i with
+        ``recv_index[i] == s``, in ascending i, of ``w_i * slice_i`` — the
+        product rounded to float32, then added in float32, one cast at the
+        end. A weight of 0 on a NaN slice stays NaN.
+
+        ``send_weights`` (length ``sum(send_counts)``): stream slice i is
+        ``w_i * tensor[send_index[i]]`` formed in float32 and quantized from
+        there, never rounded to a 16-bit dtype. Not differentiable: a
+        send weight that requires grad is refused.
+
+        A world of one returns the exact, uncompressed weighted sum.
+
+        Backward, for a call with ``recv_weights = w``: the tensor's gradient
+        is this op on the incoming gradient with counts and indices swapped
+        and ``send_weights = w`` (the exact adjoint, quantization
+        straight-through); the weights' gradient is ``gw_i = sum_a
+        slice_i[a] * grad[recv_index[i]][a]``, computed locally by a fused
+        gfx950 kernel from the wire bytes the forward received (33/32 byte
+        per element, kept only when ``w`` requires grad), deterministic, and
+        cast to ``w``'s dtype.
+        """
+        return self._comm.AlltoallPairwiseCompressedWeighted(
+            tensor, axis, send_counts, recv_counts, send_index, send_weights,
+            recv_index, recv_weights, out_size, max_repeat)
+
     def Iallreduce(self, tensor: torch.Tensor, op: int) -> WaitHandle:
         """Non-blocking Allreduce (no autograd): returns a WaitHandle whose
         Wait() yields the reduced tensor. The overlap primitive behind

@@ -25,6 +25,15 @@ dispatch gathers token order // k while it quantizes and the combine adds the
 k received rows of a token in fp32 while it dequantizes, so neither the
 gathered tokens nor an [N*k, D] combine buffer is materialised. top_k=1 takes
 the two top-1 paths above, untouched.
+
+gate_at="combine" (top_k > 1 with compression="mxfp8" only) applies the gate
+on the token's home rank instead: the combine is
+AlltoallPairwiseCompressedWeighted with the gates as receive weights, so the
+expert output is quantized ungated, the gate multiplies in fp32 inside the
+kernel that sums, and the gates never travel. A layer step then has two token
+transfers and the id transfer in forward and two token transfers in backward,
+against three transfers each way with the default "owner", and the router's
+gradient is a fused dot on the home rank.
 """
 
 import torch
@@ -34,7 +43,8 @@ import mpi4torch_amd as m4a
 
 class ExpertParallelMoE(torch.nn.Module):
     def __init__(self, d_model: int, n_experts: int, comm=None,
-                 d_hidden: int = None, compression=None, top_k: int = 1):
+                 d_hidden: int = None, compression=None, top_k: int = 1,
+                 gate_at: str = "owner"):
         super().__init__()
         if compression not in (None, "mxfp8"):
             raise ValueError(
@@ -44,8 +54,19 @@ class ExpertParallelMoE(torch.nn.Module):
             raise ValueError(
                 "mpi4torch_amd ExpertParallelMoE: top_k must lie in "
                 f"[1, n_experts = {n_experts}], got {top_k!r}")
+        if gate_at not in ("owner", "combine"):
+            raise ValueError(
+                "mpi4torch_amd ExpertParallelMoE: gate_at must be 'owner' or "
+                f"'combine', got {gate_at!r}")
+        if gate_at == "combine" and not (top_k > 1 and compression == "mxfp8"):
+            raise ValueError(
+                "mpi4torch_amd ExpertParallelMoE: gate_at='combine' needs "
+                "top_k > 1 and compression='mxfp8' (the gate rides in the "
+                f"weighted mxfp8 combine), got top_k={top_k!r}, "
+                f"compression={compression!r}")
         self.compression = compression
         self.top_k = top_k
+        self.gate_at = gate_at
         self.comm = comm if comm is not None else m4a.COMM_WORLD
         P = self.comm.size
         assert n_experts % P == 0, (
@@ -160,6 +181,15 @@ class ExpertParallelMoE(torch.nn.Module):
         eid = self.comm.AlltoallPairwise(
             expert.index_select(0, order).to(torch.float64).unsqueeze(1), 0,
             send_counts, recv_counts).squeeze(1).long()
+        if self.gate_at == "combine":
+            # the gate stays home: it weights the k received rows of a token
+            # in fp32 while the combine sums them
+            local_eid = eid - self.comm.rank * self.experts_per_rank
+            return self.comm.AlltoallPairwiseCompressedWeighted(
+                self._run_experts(dispatched, local_eid), 0, recv_counts,
+                send_counts, recv_index=tok,
+                recv_weights=gate.reshape(-1).index_select(0, order),
+                out_size=N, max_repeat=k)
         g = self.comm.AlltoallPairwise(
             gate.reshape(-1).index_select(0, order).unsqueeze(1), 0,
             send_counts, recv_counts)

@@ -111,6 +111,22 @@ def alltoall_pairwise_compressed_indexed(tensor: torch.Tensor, axis: int,
         send_index, recv_index, out_size, max_repeat)
 
 
+def alltoall_pairwise_compressed_weighted(tensor: torch.Tensor, axis: int,
+                                          send_counts, recv_counts=None, *,
+                                          send_index=None, send_weights=None,
+                                          recv_index=None, recv_weights=None,
+                                          out_size=None, max_repeat=1,
+                                          comm=None):
+    """The indexed mxfp8 pairwise all-to-all with a weight per stream slice:
+    gates applied in fp32 inside the combine, their gradient a fused dot."""
+    return _comm(comm).AlltoallPairwiseCompressedWeighted(
+        tensor, axis, list(send_counts),
+        [] if recv_counts is None else list(recv_counts),
+        send_index=send_index, send_weights=send_weights,
+        recv_index=recv_index, recv_weights=recv_weights, out_size=out_size,
+        max_repeat=max_repeat)
+
+
 def iallreduce(tensor: torch.Tensor, op: Optional[int] = None, comm=None):
     return _comm(comm).Iallreduce(tensor, _m.MPI_SUM if op is None else op)
 

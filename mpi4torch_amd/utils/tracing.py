@@ -177,6 +177,17 @@ class TracedCommunicator:
                 tensor, axis, send_counts, recv_counts, send_index,
                 recv_index, out_size, max_repeat))
 
+    def AlltoallPairwiseCompressedWeighted(self, tensor, axis, send_counts,
+                                           recv_counts, send_index=None,
+                                           send_weights=None, recv_index=None,
+                                           recv_weights=None, out_size=None,
+                                           max_repeat=1):
+        return self._record(
+            "AlltoallPairwiseCompressedWeighted", tensor,
+            lambda: self._comm.AlltoallPairwiseCompressedWeighted(
+                tensor, axis, send_counts, recv_counts, send_index,
+                send_weights, recv_index, recv_weights, out_size, max_repeat))
+
     def Iallreduce(self, tensor, op):
         return self._record("Iallreduce", tensor,
                             lambda: self._comm.Iallreduce(tensor, op))

@@ -11,6 +11,7 @@ reported GB/s counts actual bytes touched. Run on an MI355X box:
     python tools/kernel_microbench.py --mx8-quantize-blocks     # only that part
     python tools/kernel_microbench.py --mx8-segments            # only that part
     python tools/kernel_microbench.py --mx8-combine             # only that part
+    python tools/kernel_microbench.py --mx8-weighted            # only that part
 
 The mxfp8 section times the three codec kernels and, in the same run and
 alternating with it, the sibling fp8_reduce kernel at the same P and n, so
@@ -25,7 +26,10 @@ plus mx8_quantize. The segments part does the same for the pairwise
 all-to-all head and tail with a fused token permute, mx8_quantize_segments
 and mx8_dequantize_segments, against index_select plus the flat codec kernel.
 The combine part times the top-k tail mx8_dequantize_combine against
-mx8_dequantize_segments plus a torch gather-and-sum or index_add_.
+mx8_dequantize_segments plus a torch gather-and-sum or index_add_. The
+weighted part times the gated tail mx8_dequantize_combine_weighted against the
+unweighted kernel and against the sequence it replaces, and the gate gradient
+mx8_dequantize_rowdot against its sequence.
 """
 
 import os
@@ -572,6 +576,85 @@ def mx8_combine_section(repeats=5):
               flush=True)
 
 
+def mx8_weighted_section(repeats=5):
+    """The gated top-k tail at the combine geometry above (64Ki tokens x 4096,
+    k = 2, the 8 uneven segments, bf16), the same protocol: 5 repeats of 30
+    launches, sides alternating in one run, median with min-max.
+      (a) mx8_dequantize_combine_weighted against mx8_dequantize_combine,
+          table builds included on both sides;
+      (b) the weighted combine against what it replaces: dequantize_segments
+          into [N*k, D], times the gate (cast to the tensor dtype, so the
+          multiply is in bf16 where the owner path promotes to fp32),
+          index_select.view(N, k, D).sum(1);
+      (c) mx8_dequantize_rowdot against dequantize_segments +
+          g.index_select(0, t) + (v*g).sum(1)."""
+    C = m._C
+    med = lambda v: sorted(v)[len(v) // 2]
+    N, D, k, dtype = 64 << 10, 4096, 2, torch.bfloat16
+    counts = [20000, 0, 12000, 24000, 8000, 30000, 17072, 20000]
+    R = N * k
+    assert sum(counts) == R
+    gen = torch.Generator(device="cuda").manual_seed(11)
+    tok = torch.randperm(R, device="cuda", generator=gen) // k
+    inverse = torch.argsort(tok, stable=True)
+    w = torch.rand(R, device="cuda")
+    g = (torch.randn(N, D, device="cuda") * 0.2).to(dtype)
+    pay, sc = C._mx8_quantize(
+        (torch.randn(R, D, device="cuda") * 0.2).to(dtype).view(-1))
+
+    def dq():
+        return C._mx8_dequantize_segments(pay, sc, 1, D, counts,
+                                          dtype).view(R, D)
+
+    parts = {
+        "a": {
+            "fused weighted combine (with tables)":
+                lambda: C._mx8_dequantize_combine_weighted(
+                    pay, sc, D, counts, tok, w, N, k, dtype),
+            "(unweighted combine, with table)":
+                lambda: C._mx8_dequantize_combine(pay, sc, D, counts, tok, N,
+                                                  k, dtype),
+        },
+        "b": {
+            "fused weighted combine (with tables)":
+                lambda: C._mx8_dequantize_combine_weighted(
+                    pay, sc, D, counts, tok, w, N, k, dtype),
+            "(dequantize_segments * gate, index_select.sum)":
+                lambda: (dq() * w.unsqueeze(1).to(dtype))
+                .index_select(0, inverse).view(N, k, D).sum(1),
+        },
+        "c": {
+            "fused mx8_dequantize_rowdot":
+                lambda: C._mx8_dequantize_rowdot(pay, sc, D, counts, tok, g),
+            "(dequantize_segments, g.index_select, (v*g).sum)":
+                lambda: (dq().float() * g.index_select(0, tok).float())
+                .sum(1),
+        },
+    }
+    for tag, runs in parts.items():
+        times = {name: [] for name in runs}
+        for _ in range(repeats):
+            for name, fn in runs.items():
+                times[name].append(timeit(fn))
+        for name, ts in times.items():
+            print(f"(weighted {tag}) {name:50s} {med(ts)*1e3:9.1f} us  (min "
+                  f"{min(ts)*1e3:.1f} max {max(ts)*1e3:.1f} us, {len(ts)} "
+                  "repeats)", flush=True)
+        fused = med(next(ts for n, ts in times.items() if n[0] != "("))
+        other = next(ts for n, ts in times.items() if n[0] == "(")
+        print(f"(weighted {tag}) fused median "
+              f"{'below' if fused < min(other) else 'NOT below'} the other "
+              f"side's minimum ({min(other)*1e3:.1f} us), ratio to its median "
+              f"{fused/med(other):.3f}, its spread "
+              f"{min(other)/med(other):.3f}-{max(other)/med(other):.3f}",
+              flush=True)
+
+
+if "--mx8-weighted" in sys.argv:
+    mx8_weighted_section()
+    dist.destroy_process_group()
+    sys.exit(0)
+
 if "--mx8-combine" in sys.argv:
     mx8_combine_section()
     dist.destroy_process_group()
@@ -604,6 +687,7 @@ if "--mx8" in sys.argv:
     mx8_quantize_blocks_section()
     mx8_segments_section()
     mx8_combine_section()
+    mx8_weighted_section()
     dist.destroy_process_group()
     sys.exit(0)
 
