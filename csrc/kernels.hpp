@@ -202,7 +202,7 @@ void launch_mx8_dequantize_combine(const void* payload, const void* scales,
 //   acc = acc + fl(w_j * dq(src[s][j])) for j = 1..fan-1, -1 skipped;
 // then one RNE cast. The product is rounded before the add (no FMA), so the
 // torch composite acc + w*v gives the same bits; NaN follows IEEE through the
-// product (0 * NaN is NaN).
+// product (0 * NaN is NaN). A null `wsrc` is launch_mx8_dequantize_combine.
 void launch_mx8_dequantize_combine_weighted(
     const void* payload, const void* scales, const int64_t* src,
     const float* wsrc, void* out, int64_t out_slices, int fan, int64_t after,

@@ -658,9 +658,12 @@ struct BlockMap {
 // group needs no scalar tail. bs has any alignment: store_scales falls back
 // to per-lane bytes. pre(i, x) may rework the elements of stream chunk
 // i < chunks before they are quantized (the weighted head scales them).
+// pre.elem(c, v) is the same hook for the general twins, which walk single
+// elements: the value of an element of stream slice c.
 struct NoPre {
   template <typename I, int N>
   __device__ void operator()(I, float (&)[N]) const {}
+  __device__ float elem(long long, float v) const { return v; }
 };
 
 template <int K, typename I, typename Map, typename Pre = NoPre>
@@ -997,20 +1000,24 @@ struct SegCursor {
   }
 };
 
-template <int K, bool IDX>
-__global__ __launch_bounds__(256) void mx8_quantize_segments_kernel_scalar(
+// The quantizing twin's walk over segment d, one thread per group. An
+// element past the stream is a zero; one whose slice index is outside
+// [0, S) is pre.elem(c, 0): a weight still multiplies it. Inlined by force,
+// like the combine bodies below: the kernel is then optimised as the one
+// function it used to be (left to the inliner's own time, the 32-element
+// loop is unrolled in the body first and the code grows 2.5 times).
+template <int K, bool IDX, typename Pre = NoPre>
+__device__ __forceinline__ void quantize_segment_scalar(
     const void* __restrict__ in, const long long* __restrict__ idx,
-    u8* __restrict__ pay, u8* __restrict__ sc, SegArgs segs, long long S,
-    long long after, long long rows) {
+    u8* __restrict__ pay, u8* __restrict__ sc, const Mx8SegDesc& d,
+    long long S, long long after, long long rows, long long first,
+    long long stride, const Pre& pre = Pre{}) {
   using T = typename Elem<K>::type;
-  const Mx8SegDesc& d = segs.s[blockIdx.y];
   if (d.count == 0) return;
   SegCursor<IDX> cur(d, idx, S, after, rows);
   const long long G = (cur.L + 31) / 32;
   const T* __restrict__ src = reinterpret_cast<const T*>(in);
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < G;
-       g += stride) {
+  for (long long g = first; g < G; g += stride) {
     cur.seek(g * 32);
     float x[32];
     for (int k = 0; k < 32; ++k) {
@@ -1018,11 +1025,21 @@ __global__ __launch_bounds__(256) void mx8_quantize_segments_kernel_scalar(
       if (cur.in_stream()) {
         const long long o = cur.offset();
         if (o >= 0) x[k] = elem_to_f32<K>(src[o]);
+        x[k] = pre.elem(cur.c, x[k]);
         cur.advance();
       }
     }
     encode_group_scalar(x, pay + (d.goff + g) * 32, sc + d.goff + g);
   }
+}
+
+template <int K, bool IDX>
+__global__ __launch_bounds__(256) void mx8_quantize_segments_kernel_scalar(
+    const void* __restrict__ in, const long long* __restrict__ idx,
+    u8* __restrict__ pay, u8* __restrict__ sc, SegArgs segs, long long S,
+    long long after, long long rows) {
+  quantize_segment_scalar<K, IDX>(in, idx, pay, sc, segs.s[blockIdx.y], S,
+                                  after, rows, MX8_GRID_STRIDE(long long));
 }
 
 template <int K, bool IDX>
@@ -1075,7 +1092,8 @@ __device__ inline float add_single(float a, float b) {
 
 // pre() of quantize_stream: chunk i belongs to stream slice i / cps of the
 // segment, whose weight is one cached 4-byte load shared by the slice's
-// chunks (the division is the map's own).
+// chunks (the division is the map's own). elem() is the general twins' form:
+// they know the slice.
 template <typename I>
 struct SliceWeight {
   const float* __restrict__ w;  // the segment's first weight
@@ -1084,6 +1102,9 @@ struct SliceWeight {
   __device__ void operator()(I i, float (&x)[N]) const {
     const float wi = w[i / cps];
     for (int k = 0; k < N; ++k) x[k] = mul_single(wi, x[k]);
+  }
+  __device__ float elem(long long c, float v) const {
+    return mul_single(w[c], v);
   }
 };
 
@@ -1103,35 +1124,17 @@ __global__ __launch_bounds__(256) void mx8_quantize_segments_weighted_kernel(
 }
 
 // General twin: the segments twin's walk with the weight of the cursor's
-// stream slice.
+// stream slice (cps counts elements here).
 template <int K, bool IDX>
 __global__ __launch_bounds__(256)
 void mx8_quantize_segments_weighted_kernel_scalar(
     const void* __restrict__ in, const long long* __restrict__ idx,
     const float* __restrict__ wt, u8* __restrict__ pay, u8* __restrict__ sc,
     SegArgs segs, long long S, long long after) {
-  using T = typename Elem<K>::type;
   const Mx8SegDesc& d = segs.s[blockIdx.y];
-  if (d.count == 0) return;
-  SegCursor<IDX> cur(d, idx, S, after, 1);
-  const long long G = (cur.L + 31) / 32;
-  const T* __restrict__ src = reinterpret_cast<const T*>(in);
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < G;
-       g += stride) {
-    cur.seek(g * 32);
-    float x[32];
-    for (int k = 0; k < 32; ++k) {
-      x[k] = 0.0f;
-      if (cur.in_stream()) {
-        const long long o = cur.offset();
-        x[k] = mul_single(wt[d.displ + cur.c],
-                         o >= 0 ? elem_to_f32<K>(src[o]) : 0.0f);
-        cur.advance();
-      }
-    }
-    encode_group_scalar(x, pay + (d.goff + g) * 32, sc + d.goff + g);
-  }
+  quantize_segment_scalar<K, IDX>(
+      in, idx, pay, sc, d, S, after, 1, MX8_GRID_STRIDE(long long),
+      SliceWeight<long long>{wt + d.displ, after});
 }
 
 // ---- dequantize_combine (the top-k pairwise all-to-all tail) --------------
@@ -1160,125 +1163,72 @@ void mx8_quantize_segments_weighted_kernel_scalar(
 // scale load of the batch, are issued before the first value is consumed, so
 // a lane keeps up to four payload loads in flight for its one 16-byte store
 // and the staging stays in registers.
-constexpr int kCombineBatch = 4;
-
-template <int K, typename I>
-__global__ __launch_bounds__(256) void mx8_dequantize_combine_kernel(
-    const u8* __restrict__ pay, const u8* __restrict__ sc,
-    const long long* __restrict__ src, void* __restrict__ out, I chunks,
-    I cps, int fan) {
-  constexpr int EPL = kEPL<K>;
-  const I stride = (I)gridDim.x * blockDim.x;
-  for (I i = (I)blockIdx.x * blockDim.x + threadIdx.x; i < chunks;
-       i += stride) {
-    const I s = i / cps;
-    const long long col = (long long)(i - s * cps) * EPL;
-    const long long* __restrict__ t = src + (long long)s * fan;
-    float acc[EPL];
-    for (int k = 0; k < EPL; ++k) acc[k] = 0.0f;
-    for (int j0 = 0; j0 < fan; j0 += kCombineBatch) {
-      long long o[kCombineBatch];
-      unsigned w[kCombineBatch][EPL / 4];
-      int sb[kCombineBatch];
-#pragma unroll
-      for (int u = 0; u < kCombineBatch; ++u) {
-        o[u] = j0 + u < fan ? t[j0 + u] : -1;
-      }
-#pragma unroll
-      for (int u = 0; u < kCombineBatch; ++u) {
-        if (o[u] >= 0) {
-          const long long b = o[u] + col;
-          load_payload<EPL>(pay, b / EPL, w[u]);
-          sb[u] = sc[b >> 5];
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < kCombineBatch; ++u) {
-        if (o[u] >= 0) {
-          // source 0 is assigned (it keeps a -0.0), the others are added
-          const bool first = u == 0 && j0 == 0;
-          for (int d = 0; d < EPL / 4; ++d) {
-            for (int k = 0; k < 4; ++k) {
-              const float v = mx8_dequant((u8)(w[u][d] >> (8 * k)), sb[u]);
-              acc[4 * d + k] = first ? v : acc[4 * d + k] + v;
-            }
-          }
-        }
-      }
-    }
-    __builtin_nontemporal_store(pack16<K, EPL>(acc),
-                                reinterpret_cast<v4u*>(out) + i);
-  }
-}
-
-// General twin: any `after`, any alignment of the bases. One thread per
-// output element with the same source loop; token rows never take it.
-template <int K>
-__global__ __launch_bounds__(256) void mx8_dequantize_combine_kernel_scalar(
-    const u8* __restrict__ pay, const u8* __restrict__ sc,
-    const long long* __restrict__ src, void* __restrict__ out,
-    long long total, long long after, int fan) {
-  using T = typename Elem<K>::type;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-       e < total; e += stride) {
-    const long long s = e / after;
-    const long long a = e - s * after;
-    const long long* __restrict__ t = src + s * fan;
-    float acc = 0.0f;
-    for (int j = 0; j < fan; ++j) {
-      const long long o = t[j];
-      if (o < 0) continue;
-      const float v = mx8_dequant(pay[o + a], sc[(o + a) >> 5]);
-      acc = j == 0 ? v : acc + v;
-    }
-    reinterpret_cast<T*>(out)[e] = f32_to_elem<K>(acc);
-  }
-}
-
-// ---- dequantize_combine_weighted (the gated top-k tail) --------------------
 //
-// dequantize_combine with one fp32 weight per table entry: wsrc is a table
-// [out_slices][fan] parallel to src. The vector body loads a weight with its
-// offset, before it knows the offset's sign, so every entry must be
-// initialised; one whose offset is -1 is never used (the host writes 0).
-// Rule, per output element, in fp32:
+// The weighted form (the gated top-k tail) has one fp32 weight per table
+// entry: wsrc is a table [out_slices][fan] parallel to src, and the rule
+// becomes, per output element, in fp32:
 //   acc = fl(w0 * dq(src[s][0])), or +0.0 when that entry is -1;
 //   acc = acc + fl(w_j * dq(src[s][j])) for j = 1..fan-1, -1 skipped;
 //   one RNE cast.
 // The product is rounded before the add: mul_single and add_single are never
 // contracted, which is what lets the torch composite acc + w*v agree bit for
 // bit. A weight of 0 on a NaN source stays NaN (IEEE through the product).
-//
-// A sibling of mx8_dequantize_combine_kernel, not an instantiation of it, so
-// that kernel is compiled from the same text as before. Same layout: flat
-// grid over the output chunks, the batch's table entries (offset and weight,
-// both cached loads shared by a slice's chunks), then its payload and scale
-// loads, all issued before the first value is consumed.
-template <int K, typename I>
-__global__ __launch_bounds__(256) void mx8_dequantize_combine_weighted_kernel(
-    const u8* __restrict__ pay, const u8* __restrict__ sc,
-    const long long* __restrict__ src, const float* __restrict__ wsrc,
-    void* __restrict__ out, I chunks, I cps, int fan) {
+// The vector body loads a weight with its offset (both cached loads shared
+// by a slice's chunks), before it knows the offset's sign, so every entry
+// must be initialised; one whose offset is -1 is never used (the host
+// writes 0).
+constexpr int kCombineBatch = 4;
+
+// The weight policy of the combine bodies: row(e) is the policy from table
+// entry e on, load(j) what entry j contributes besides its offset,
+// term(w, v) the summand of a dequantized value and add(acc, t) the
+// accumulation. NoWeight loads nothing (Val is empty) and sums the values
+// themselves with the plain acc + v.
+struct NoWeight {
+  struct Val {};
+  __device__ NoWeight row(long long) const { return {}; }
+  __device__ Val load(long long) const { return {}; }
+  __device__ static float term(Val, float v) { return v; }
+  __device__ static float add(float acc, float t) { return acc + t; }
+};
+
+struct TableWeight {
+  using Val = float;
+  const float* __restrict__ wsrc;
+  __device__ TableWeight row(long long e) const { return {wsrc + e}; }
+  __device__ float load(long long j) const { return wsrc[j]; }
+  __device__ static float term(float w, float v) { return mul_single(w, v); }
+  __device__ static float add(float acc, float t) {
+    return add_single(acc, t);
+  }
+};
+
+// The vector body over output chunks first, first + stride, ... < chunks of
+// cps chunks per slice; the conditions above are the launcher's to check.
+template <int K, typename I, typename W>
+__device__ __forceinline__ void combine_stream(const u8* __restrict__ pay,
+                                      const u8* __restrict__ sc,
+                                      const long long* __restrict__ src,
+                                      void* __restrict__ out, I chunks, I cps,
+                                      int fan, I first, I stride,
+                                      const W& wt) {
   constexpr int EPL = kEPL<K>;
-  const I stride = (I)gridDim.x * blockDim.x;
-  for (I i = (I)blockIdx.x * blockDim.x + threadIdx.x; i < chunks;
-       i += stride) {
+  for (I i = first; i < chunks; i += stride) {
     const I s = i / cps;
     const long long col = (long long)(i - s * cps) * EPL;
     const long long* __restrict__ t = src + (long long)s * fan;
-    const float* __restrict__ tw = wsrc + (long long)s * fan;
+    const W tw = wt.row((long long)s * fan);
     float acc[EPL];
     for (int k = 0; k < EPL; ++k) acc[k] = 0.0f;
     for (int j0 = 0; j0 < fan; j0 += kCombineBatch) {
       long long o[kCombineBatch];
-      float wj[kCombineBatch];
+      typename W::Val wj[kCombineBatch];
       unsigned w[kCombineBatch][EPL / 4];
       int sb[kCombineBatch];
 #pragma unroll
       for (int u = 0; u < kCombineBatch; ++u) {
         o[u] = j0 + u < fan ? t[j0 + u] : -1;
-        wj[u] = j0 + u < fan ? tw[j0 + u] : 0.0f;
+        wj[u] = j0 + u < fan ? tw.load(j0 + u) : typename W::Val{};
       }
 #pragma unroll
       for (int u = 0; u < kCombineBatch; ++u) {
@@ -1295,9 +1245,9 @@ __global__ __launch_bounds__(256) void mx8_dequantize_combine_weighted_kernel(
           const bool first = u == 0 && j0 == 0;
           for (int d = 0; d < EPL / 4; ++d) {
             for (int k = 0; k < 4; ++k) {
-              const float v = mul_single(
+              const float v = W::term(
                   wj[u], mx8_dequant((u8)(w[u][d] >> (8 * k)), sb[u]));
-              acc[4 * d + k] = first ? v : add_single(acc[4 * d + k], v);
+              acc[4 * d + k] = first ? v : W::add(acc[4 * d + k], v);
             }
           }
         }
@@ -1308,29 +1258,68 @@ __global__ __launch_bounds__(256) void mx8_dequantize_combine_weighted_kernel(
   }
 }
 
-// General twin: any `after`, any alignment of the bases.
-template <int K>
-__global__ __launch_bounds__(256)
-void mx8_dequantize_combine_weighted_kernel_scalar(
-    const u8* __restrict__ pay, const u8* __restrict__ sc,
-    const long long* __restrict__ src, const float* __restrict__ wsrc,
-    void* __restrict__ out, long long total, long long after, int fan) {
+// The general twins' body: any `after`, any alignment of the bases. One
+// thread per output element with the same source loop; token rows never take
+// it.
+template <int K, typename W>
+__device__ __forceinline__ void combine_scalar(const u8* __restrict__ pay,
+                                      const u8* __restrict__ sc,
+                                      const long long* __restrict__ src,
+                                      void* __restrict__ out, long long total,
+                                      long long after, int fan,
+                                      long long first, long long stride,
+                                      const W& wt) {
   using T = typename Elem<K>::type;
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-       e < total; e += stride) {
+  for (long long e = first; e < total; e += stride) {
     const long long s = e / after;
     const long long a = e - s * after;
     float acc = 0.0f;
     for (int j = 0; j < fan; ++j) {
       const long long o = src[s * fan + j];
       if (o < 0) continue;
-      const float v = mul_single(wsrc[s * fan + j],
-                                mx8_dequant(pay[o + a], sc[(o + a) >> 5]));
-      acc = j == 0 ? v : add_single(acc, v);
+      const float v = W::term(wt.load(s * fan + j),
+                              mx8_dequant(pay[o + a], sc[(o + a) >> 5]));
+      acc = j == 0 ? v : W::add(acc, v);
     }
     reinterpret_cast<T*>(out)[e] = f32_to_elem<K>(acc);
   }
+}
+
+template <int K, typename I>
+__global__ __launch_bounds__(256) void mx8_dequantize_combine_kernel(
+    const u8* __restrict__ pay, const u8* __restrict__ sc,
+    const long long* __restrict__ src, void* __restrict__ out, I chunks,
+    I cps, int fan) {
+  combine_stream<K, I>(pay, sc, src, out, chunks, cps, fan,
+                       MX8_GRID_STRIDE(I), NoWeight{});
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void mx8_dequantize_combine_kernel_scalar(
+    const u8* __restrict__ pay, const u8* __restrict__ sc,
+    const long long* __restrict__ src, void* __restrict__ out,
+    long long total, long long after, int fan) {
+  combine_scalar<K>(pay, sc, src, out, total, after, fan,
+                    MX8_GRID_STRIDE(long long), NoWeight{});
+}
+
+template <int K, typename I>
+__global__ __launch_bounds__(256) void mx8_dequantize_combine_weighted_kernel(
+    const u8* __restrict__ pay, const u8* __restrict__ sc,
+    const long long* __restrict__ src, const float* __restrict__ wsrc,
+    void* __restrict__ out, I chunks, I cps, int fan) {
+  combine_stream<K, I>(pay, sc, src, out, chunks, cps, fan,
+                       MX8_GRID_STRIDE(I), TableWeight{wsrc});
+}
+
+template <int K>
+__global__ __launch_bounds__(256)
+void mx8_dequantize_combine_weighted_kernel_scalar(
+    const u8* __restrict__ pay, const u8* __restrict__ sc,
+    const long long* __restrict__ src, const float* __restrict__ wsrc,
+    void* __restrict__ out, long long total, long long after, int fan) {
+  combine_scalar<K>(pay, sc, src, out, total, after, fan,
+                    MX8_GRID_STRIDE(long long), TableWeight{wsrc});
 }
 
 // ---- dequantize_rowdot (the gate gradient of the weighted tail) -----------
@@ -1651,6 +1640,27 @@ inline SegBatch seg_batch(const Mx8SegDesc* segs, int n) {
   return b;
 }
 
+// f(batch) for every launch's worth of the segments that has a non-empty one.
+template <typename F>
+void for_seg_batches(const Mx8SegDesc* segs, int nsegs, F&& f) {
+  for (int s0 = 0; s0 < nsegs; s0 += kMaxMx8SegsPerLaunch) {
+    const int n = nsegs - s0 < kMaxMx8SegsPerLaunch ? nsegs - s0
+                                                    : kMaxMx8SegsPerLaunch;
+    const SegBatch b = seg_batch(segs + s0, n);
+    if (b.max_count > 0) f(b);
+  }
+}
+
+// f(std::bool_constant<indexed>) for a general twin or a rows == 1 MODE
+template <typename F>
+void by_indexed(const long long* idx, F&& f) {
+  if (idx == nullptr) {
+    f(std::false_type{});
+  } else {
+    f(std::true_type{});
+  }
+}
+
 // With no index, rows == 1 and every L_p a multiple of 32, segments that
 // follow each other on both sides form one flat mxfp8 stream. Returns its
 // element count, or -1 when the segments are not of that shape; *first
@@ -1712,11 +1722,8 @@ void launch_segments_t(std::conditional_t<Q, const void, void>* tensor,
       }
     }
   }
-  for (int s0 = 0; s0 < nsegs; s0 += kMaxMx8SegsPerLaunch) {
-    const int n = nsegs - s0 < kMaxMx8SegsPerLaunch ? nsegs - s0
-                                                    : kMaxMx8SegsPerLaunch;
-    const SegBatch b = seg_batch(segs + s0, n);
-    if (b.max_count == 0) continue;
+  for_seg_batches(segs, nsegs, [&](const SegBatch& b) {
+    const int n = b.n;
     if (al && after % EPL == 0) {
       const long long cps = after / EPL;
       const long long chunks = rows * b.max_count * cps;
@@ -1739,7 +1746,7 @@ void launch_segments_t(std::conditional_t<Q, const void, void>* tensor,
       });
     } else {
       const long long G = (rows * b.max_count * after + 31) / 32;
-      auto twin = [&](auto indexed) {
+      by_indexed(idx, [&](auto indexed) {
         constexpr bool IDX = decltype(indexed)::value;
         if constexpr (Q) {
           hipLaunchKernelGGL((mx8_quantize_segments_kernel_scalar<K, IDX>),
@@ -1752,21 +1759,18 @@ void launch_segments_t(std::conditional_t<Q, const void, void>* tensor,
                              tensor, b.args, (long long)S, (long long)after,
                              (long long)rows);
         }
-      };
-      if (idx == nullptr) {
-        twin(std::false_type{});
-      } else {
-        twin(std::true_type{});
-      }
+      });
     }
-  }
+  });
 }
 
+// Both combine launchers: wsrc is the weight table, null for the unweighted
+// kernels, which take no such argument.
 template <int K>
 void launch_dequantize_combine_t(const u8* pay, const u8* sc,
-                                 const long long* src, void* out,
-                                 int64_t out_slices, int fan, int64_t after,
-                                 hipStream_t stream) {
+                                 const long long* src, const float* wsrc,
+                                 void* out, int64_t out_slices, int fan,
+                                 int64_t after, hipStream_t stream) {
   constexpr int EPL = kEPL<K>;
   // Every slice offset is 32*goff + c*after, a multiple of EPL when after
   // is, so a payload base aligned to EPL keeps every chunk's load aligned.
@@ -1775,40 +1779,29 @@ void launch_dequantize_combine_t(const u8* pay, const u8* sc,
     const long long chunks = out_slices * cps;
     by_width(chunks, [&](auto i) {
       using I = decltype(i);
-      hipLaunchKernelGGL((mx8_dequantize_combine_kernel<K, I>),
-                         dim3(grid_for(chunks)), dim3(256), 0, stream, pay, sc,
-                         src, out, (I)chunks, (I)cps, fan);
+      const dim3 grid(grid_for(chunks));
+      if (wsrc == nullptr) {
+        hipLaunchKernelGGL((mx8_dequantize_combine_kernel<K, I>), grid,
+                           dim3(256), 0, stream, pay, sc, src, out, (I)chunks,
+                           (I)cps, fan);
+      } else {
+        hipLaunchKernelGGL((mx8_dequantize_combine_weighted_kernel<K, I>),
+                           grid, dim3(256), 0, stream, pay, sc, src, wsrc, out,
+                           (I)chunks, (I)cps, fan);
+      }
     });
   } else {
     const long long total = out_slices * after;
-    hipLaunchKernelGGL((mx8_dequantize_combine_kernel_scalar<K>),
-                       dim3(grid_for(total)), dim3(256), 0, stream, pay, sc,
-                       src, out, total, (long long)after, fan);
-  }
-}
-
-template <int K>
-void launch_dequantize_combine_weighted_t(const u8* pay, const u8* sc,
-                                          const long long* src,
-                                          const float* wsrc, void* out,
-                                          int64_t out_slices, int fan,
-                                          int64_t after, hipStream_t stream) {
-  constexpr int EPL = kEPL<K>;
-  // the conditions of launch_dequantize_combine_t
-  if (after % EPL == 0 && aligned(out, 16) && aligned(pay, EPL)) {
-    const long long cps = after / EPL;
-    const long long chunks = out_slices * cps;
-    by_width(chunks, [&](auto i) {
-      using I = decltype(i);
-      hipLaunchKernelGGL((mx8_dequantize_combine_weighted_kernel<K, I>),
-                         dim3(grid_for(chunks)), dim3(256), 0, stream, pay, sc,
-                         src, wsrc, out, (I)chunks, (I)cps, fan);
-    });
-  } else {
-    const long long total = out_slices * after;
-    hipLaunchKernelGGL((mx8_dequantize_combine_weighted_kernel_scalar<K>),
-                       dim3(grid_for(total)), dim3(256), 0, stream, pay, sc,
-                       src, wsrc, out, total, (long long)after, fan);
+    const dim3 grid(grid_for(total));
+    if (wsrc == nullptr) {
+      hipLaunchKernelGGL((mx8_dequantize_combine_kernel_scalar<K>), grid,
+                         dim3(256), 0, stream, pay, sc, src, out, total,
+                         (long long)after, fan);
+    } else {
+      hipLaunchKernelGGL((mx8_dequantize_combine_weighted_kernel_scalar<K>),
+                         grid, dim3(256), 0, stream, pay, sc, src, wsrc, out,
+                         total, (long long)after, fan);
+    }
   }
 }
 
@@ -1823,45 +1816,31 @@ void launch_quantize_segments_weighted_t(const void* in, const long long* idx,
   constexpr int LPG = kLPG<K>;
   constexpr int EPL = kEPL<K>;
   const bool al = aligned(in, 16) && aligned(pay, 32 / LPG);
-  for (int s0 = 0; s0 < nsegs; s0 += kMaxMx8SegsPerLaunch) {
-    const int n = nsegs - s0 < kMaxMx8SegsPerLaunch ? nsegs - s0
-                                                    : kMaxMx8SegsPerLaunch;
-    const SegBatch b = seg_batch(segs + s0, n);
-    if (b.max_count == 0) continue;
+  for_seg_batches(segs, nsegs, [&](const SegBatch& b) {
     if (al && after % EPL == 0) {
       const long long cps = after / EPL;
       const long long work = (b.max_count * cps + LPG - 1) / LPG * LPG;
       by_width(work, [&](auto i) {
         using I = decltype(i);
-        auto go = [&](auto mode) {
+        by_indexed(idx, [&](auto indexed) {
+          constexpr int MODE = decltype(indexed)::value ? 1 : 0;
           hipLaunchKernelGGL(
-              (mx8_quantize_segments_weighted_kernel<K, I,
-                                                     decltype(mode)::value>),
-              grid2d(work, n), dim3(256), 0, stream, in, idx, wt, pay, sc,
+              (mx8_quantize_segments_weighted_kernel<K, I, MODE>),
+              grid2d(work, b.n), dim3(256), 0, stream, in, idx, wt, pay, sc,
               b.args, (long long)S, (I)cps);
-        };
-        if (idx == nullptr) {
-          go(Tag<0>{});
-        } else {
-          go(Tag<1>{});
-        }
+        });
       });
     } else {
       const long long G = (b.max_count * after + 31) / 32;
-      auto twin = [&](auto indexed) {
+      by_indexed(idx, [&](auto indexed) {
         constexpr bool IDX = decltype(indexed)::value;
         hipLaunchKernelGGL(
             (mx8_quantize_segments_weighted_kernel_scalar<K, IDX>),
-            grid2d(G, n), dim3(256), 0, stream, in, idx, wt, pay, sc, b.args,
+            grid2d(G, b.n), dim3(256), 0, stream, in, idx, wt, pay, sc, b.args,
             (long long)S, (long long)after);
-      };
-      if (idx == nullptr) {
-        twin(std::false_type{});
-      } else {
-        twin(std::true_type{});
-      }
+      });
     }
-  }
+  });
 }
 
 template <int K>
@@ -1910,7 +1889,7 @@ void launch_mx8_dequantize_combine_weighted(
     int dtype, hipStream_t stream) {
   if (out_slices <= 0 || after <= 0 || fan <= 0) return;
   by_dtype(dtype, [&](auto k) {
-    launch_dequantize_combine_weighted_t<k>(
+    launch_dequantize_combine_t<k>(
         static_cast<const u8*>(payload), static_cast<const u8*>(scales),
         reinterpret_cast<const long long*>(src), wsrc, out, out_slices, fan,
         after, stream);
@@ -1949,13 +1928,9 @@ void launch_mx8_dequantize_combine(const void* payload, const void* scales,
                                    const int64_t* src, void* out,
                                    int64_t out_slices, int fan, int64_t after,
                                    int dtype, hipStream_t stream) {
-  if (out_slices <= 0 || after <= 0 || fan <= 0) return;
-  by_dtype(dtype, [&](auto k) {
-    launch_dequantize_combine_t<k>(static_cast<const u8*>(payload),
-                                   static_cast<const u8*>(scales),
-                                   reinterpret_cast<const long long*>(src),
-                                   out, out_slices, fan, after, stream);
-  });
+  launch_mx8_dequantize_combine_weighted(payload, scales, src, nullptr, out,
+                                         out_slices, fan, after, dtype,
+                                         stream);
 }
 
 void launch_mx8_quantize_segments(const void* in, const int64_t* idx,

@@ -1212,11 +1212,17 @@ Mx8SegPlan mx8_seg_plan(const std::vector<int64_t>& counts, int64_t rows,
 // partial last group is zero-padded. Returns (payload [32*sum G_p], scales
 // [sum G_p]) with the segments' streams one after the other. sum(counts)
 // must equal S without an order and the order's length with one.
+//
+// With `weights` (fp32 [sum(counts)], rows == 1) stream slice i is
+// fl32(w_i * f32(in[order_i])) (in[i] without an order), an order entry
+// outside [0, S) reading as zeros; segment p is mx8_quantize of its fp32
+// products. The product never rounds to in's dtype.
 std::pair<Tensor, Tensor> mx8_quantize_segments(
     const Tensor& in, int64_t rows, int64_t after,
     const std::vector<int64_t>& counts, const c10::optional<Tensor>& order,
     const c10::optional<Tensor>& payload_out = c10::nullopt,
-    const c10::optional<Tensor>& scales_out = c10::nullopt) {
+    const c10::optional<Tensor>& scales_out = c10::nullopt,
+    const c10::optional<Tensor>& weights = c10::nullopt) {
   const int dt = mx8_dtype_code(in.scalar_type());
   const auto pl = mx8_seg_plan(counts, rows, after);
   const int64_t S = rows * after > 0 ? in.numel() / (rows * after) : 0;
@@ -1228,15 +1234,32 @@ std::pair<Tensor, Tensor> mx8_quantize_segments(
                                    : at::empty({pl.total_groups}, bopts);
   if (pl.total_groups == 0) return {pay, sc};
   if (in.is_cuda()) {
-    launch_mx8_quantize_segments(
-        in.data_ptr(),
-        order.has_value() ? order->data_ptr<int64_t>() : nullptr,
-        pay.data_ptr(), sc.data_ptr(), pl.segs.data(), (int)pl.segs.size(),
-        rows, S, after, dt, current_gpu_stream(in));
+    const int64_t* idx =
+        order.has_value() ? order->data_ptr<int64_t>() : nullptr;
+    if (weights.has_value()) {
+      launch_mx8_quantize_segments_weighted(
+          in.data_ptr(), idx, weights->data_ptr<float>(), pay.data_ptr(),
+          sc.data_ptr(), pl.segs.data(), (int)pl.segs.size(), S, after, dt,
+          current_gpu_stream(in));
+    } else {
+      launch_mx8_quantize_segments(
+          in.data_ptr(), idx, pay.data_ptr(), sc.data_ptr(), pl.segs.data(),
+          (int)pl.segs.size(), rows, S, after, dt, current_gpu_stream(in));
+    }
     return {pay, sc};
   }
   auto xs = in.view({rows, S, after});
-  if (order.has_value()) xs = xs.index_select(1, *order);
+  if (weights.has_value()) {
+    xs = xs.to(at::kFloat);
+    if (order.has_value()) {
+      auto ok = order->ge(0).logical_and(order->lt(S)).view({1, -1, 1});
+      xs = at::where(ok, xs.index_select(1, order->clamp(0, S > 0 ? S - 1 : 0)),
+                     at::zeros({}, xs.options()));
+    }
+    xs = weights->view({1, -1, 1}) * xs;
+  } else if (order.has_value()) {
+    xs = xs.index_select(1, *order);
+  }
   for (size_t p = 0; p < counts.size(); ++p) {
     if (pl.groups[p] == 0) continue;
     auto q = mx8_quantize(
@@ -1295,35 +1318,6 @@ Tensor mx8_dequantize_segments(const Tensor& pay, const Tensor& sc,
   return out;
 }
 
-// The pairwise all-to-all of the family: `in` is this rank's contiguous
-// tensor seen as [rows, S, after]. The fused head gathers slices through
-// send_order while it quantizes segment p (what rank p receives) in groups of
-// 32 that start at the segment; payload and scales travel as two contiguous
-// pieces per peer in ONE grouped call, their sizes 32*G and G computed from
-// the counts both ends know; the fused tail dequantizes the received
-// segments, the own one included, straight into [rows, R, after], scattering
-// slices through recv_order while it writes. No index_select pass on either
-// side; every value is quantized exactly once. Both transports skip
-// zero-length pieces on both ends of a pair, and so does this: an empty
-// segment is not listed at all.
-Tensor mx8_alltoall_pairwise(Transport& tr, const Tensor& in, int64_t rows,
-                             int64_t after,
-                             const std::vector<int64_t>& send_counts,
-                             const std::vector<int64_t>& recv_counts,
-                             const c10::optional<Tensor>& send_order,
-                             const c10::optional<Tensor>& recv_order) {
-  const auto sp = mx8_seg_plan(send_counts, rows, after);
-  const auto rp = mx8_seg_plan(recv_counts, rows, after);
-  auto q = mx8_quantize_segments(in, rows, after, send_counts, send_order);
-  auto bopts = in.options().dtype(at::kByte);
-  auto stg_pay = at::empty({rp.total_groups * 32}, bopts);
-  auto stg_sc = at::empty({rp.total_groups}, bopts);
-  mx8_exchange(tr, {q.first, q.second, sp.goffs(), sp.groups},
-               {stg_pay, stg_sc, rp.goffs(), rp.groups});
-  return mx8_dequantize_segments(stg_pay, stg_sc, rows, after, recv_counts,
-                                 recv_order, in.scalar_type());
-}
-
 // ---- the top-k tail: received slices summed where several name one slice ---
 //
 // Rule (normative; mx8_dequantize_combine_kernel matches it bit for bit): a
@@ -1332,6 +1326,12 @@ Tensor mx8_alltoall_pairwise(Transport& tr, const Tensor& in, int64_t rows,
 //   acc = v(tab[s][0]), or +0.0 when that entry is -1;
 //   acc = acc + v(tab[s][j]) for j = 1..fan-1 in that order, -1 skipped;
 // then one cast.
+//
+// The gated tail has weights w [R] fp32 next to the values (normative;
+// mx8_dequantize_combine_weighted_kernel matches it bit for bit):
+//   acc = fl(w * v)(tab[s][0]), or +0.0 when that entry is -1;
+//   acc = acc + fl(w * v)(tab[s][j]) for j = 1..fan-1, -1 skipped;
+// the product rounded to fp32 before the add (two torch ops, no FMA).
 
 // The table of `index` (int64 [R], index[i] = output slice of source i):
 // the sources of a slice in ascending i, each entered as base[i] (int64 [R],
@@ -1364,28 +1364,29 @@ std::pair<Tensor, Tensor> mx8_combine_slots(const Tensor& index,
   return {slot, perm};
 }
 
+// With `weights` (fp32 [R]) the weight table of the gated tail is built
+// parallel to it into *wtab, 0 where the offset table has -1, from the same
+// slot computation: no sync, nothing uploaded. Without them no weight table
+// exists.
 Tensor mx8_combine_table(const Tensor& index, const Tensor& base,
-                         int64_t out_size, int64_t fan) {
+                         int64_t out_size, int64_t fan,
+                         const c10::optional<Tensor>& weights = c10::nullopt,
+                         Tensor* wtab = nullptr) {
   auto table = at::full({out_size * fan + 1}, -1, index.options());
+  if (weights.has_value()) {
+    *wtab = at::zeros({out_size * fan + 1}, weights->options());
+  }
   if (index.numel() == 0) return table;
   const auto sp = mx8_combine_slots(index, out_size, fan);
   table.scatter_(0, sp.first, base.index_select(0, sp.second));
+  if (weights.has_value()) {
+    wtab->scatter_(0, sp.first, weights->index_select(0, sp.second));
+  }
   return table;
 }
 
-// The offset table and, parallel to it, the fp32 weight table of the weighted
-// tail (weights: fp32 [R]; 0 where the offset table has -1) from one slot
-// computation: no sync, nothing uploaded.
-std::pair<Tensor, Tensor> mx8_combine_tables_weighted(
-    const Tensor& index, const Tensor& base, const Tensor& weights,
-    int64_t out_size, int64_t fan) {
-  auto table = at::full({out_size * fan + 1}, -1, index.options());
-  auto wtab = at::zeros({out_size * fan + 1}, weights.options());
-  if (index.numel() == 0) return {table, wtab};
-  const auto sp = mx8_combine_slots(index, out_size, fan);
-  table.scatter_(0, sp.first, base.index_select(0, sp.second));
-  wtab.scatter_(0, sp.first, weights.index_select(0, sp.second));
-  return {table, wtab};
+Tensor table_view(const Tensor& flat, int64_t out_size, int64_t fan) {
+  return flat.narrow(0, 0, out_size * fan).view({out_size, fan});
 }
 
 // The kernel's table: every source entered as the payload byte offset of its
@@ -1403,23 +1404,20 @@ Tensor mx8_slice_offsets(const Mx8SegPlan& pl, int64_t after,
   return base;
 }
 
-Tensor mx8_combine_offsets_table(const Tensor& index, const Mx8SegPlan& pl,
-                                 int64_t after, int64_t out_size,
-                                 int64_t fan) {
-  return mx8_combine_table(index, mx8_slice_offsets(pl, after, index.options()),
-                           out_size, fan);
-}
-
-// The rule above on values v [R, after] fp32 through a table [out_size, fan]
-// of row numbers: [out_size, after] fp32, not yet cast.
-Tensor ordered_table_sum(const Tensor& v, const Tensor& tab) {
+// The rules above on values v [R, after] fp32 through a table [out_size, fan]
+// of row numbers: [out_size, after] fp32, not yet cast. Without weights no
+// multiply takes place.
+Tensor ordered_table_sum(const Tensor& v, const Tensor& tab,
+                         const c10::optional<Tensor>& w = c10::nullopt) {
   const int64_t out_size = tab.size(0), fan = tab.size(1);
   auto acc = at::zeros({out_size, v.size(1)}, v.options());
   if (v.size(0) == 0) return acc;
   for (int64_t j = 0; j < fan; ++j) {
     auto col = tab.select(1, j);
     auto ok = col.ge(0).unsqueeze(1);
-    auto term = v.index_select(0, col.clamp_min(0));
+    auto src = col.clamp_min(0);
+    auto term = v.index_select(0, src);
+    if (w.has_value()) term = w->index_select(0, src).unsqueeze(1) * term;
     acc = at::where(ok, j == 0 ? term : acc + term, acc);
   }
   return acc;
@@ -1447,15 +1445,18 @@ Tensor mx8_segment_values(const Tensor& pay, const Tensor& sc,
 // The top-k tail of the pairwise all-to-all (rows == 1): the received
 // segments' streams (layout as mx8_dequantize_segments, R = sum(counts)
 // received slices of `after` elements) are dequantized and received slice i
-// is added into output slice index[i] under the rule above, sources in
-// ascending i; slices no entry names are zeros. Returns [out_size, after] of
-// `dtype`, written into `out_opt` when given. At most `fan` sources per
-// slice: surplus and out-of-range entries are dropped.
+// is added into output slice index[i] under the rules above, sources in
+// ascending i, scaled by weights[i] (fp32 [R]) when weights are given;
+// slices no entry names are zeros. Returns [out_size, after] of `dtype`,
+// written into `out_opt` when given. At most `fan` sources per slice:
+// surplus and out-of-range entries are dropped.
 Tensor mx8_dequantize_combine(const Tensor& pay, const Tensor& sc,
                               int64_t after,
                               const std::vector<int64_t>& counts,
-                              const Tensor& index, int64_t out_size,
-                              int64_t fan, at::ScalarType dtype,
+                              const Tensor& index,
+                              const c10::optional<Tensor>& weights,
+                              int64_t out_size, int64_t fan,
+                              at::ScalarType dtype,
                               const c10::optional<Tensor>& out_opt =
                                   c10::nullopt) {
   const int dt = mx8_dtype_code(dtype);
@@ -1464,145 +1465,21 @@ Tensor mx8_dequantize_combine(const Tensor& pay, const Tensor& sc,
   if (pay.is_cuda()) {
     auto out = out_or_empty(out_opt, {out_size, after},
                             pay.options().dtype(dtype));
-    auto table = mx8_combine_offsets_table(index, pl, after, out_size, fan);
-    launch_mx8_dequantize_combine(pay.data_ptr(), sc.data_ptr(),
-                                  table.data_ptr<int64_t>(), out.data_ptr(),
-                                  out_size, (int)fan, after, dt,
-                                  current_gpu_stream(pay));
+    Tensor wtab;
+    auto table = mx8_combine_table(index, mx8_slice_offsets(pl, after, iopts),
+                                   out_size, fan, weights, &wtab);
+    launch_mx8_dequantize_combine_weighted(
+        pay.data_ptr(), sc.data_ptr(), table.data_ptr<int64_t>(),
+        wtab.defined() ? wtab.data_ptr<float>() : nullptr, out.data_ptr(),
+        out_size, (int)fan, after, dt, current_gpu_stream(pay));
     return out;
   }
   auto v = mx8_segment_values(pay, sc, pl, after);
   auto table = mx8_combine_table(index, at::arange(pl.slices, iopts), out_size,
                                  fan);
-  auto res = ordered_table_sum(
-                 v, table.narrow(0, 0, out_size * fan).view({out_size, fan}))
+  auto res = ordered_table_sum(v, table_view(table, out_size, fan), weights)
                  .to(dtype);
   return out_opt.has_value() ? out_opt->copy_(res) : res;
-}
-
-// mx8_alltoall_pairwise for the top-k case: the head gathers through
-// send_index, which may repeat slices (the quantize kernel never needed an
-// injective index); with a recv_index the tail is mx8_dequantize_combine
-// (rows == 1), without one the plain segments tail.
-Tensor mx8_alltoall_pairwise_indexed(
-    Transport& tr, const Tensor& in, int64_t rows, int64_t after,
-    const std::vector<int64_t>& send_counts,
-    const std::vector<int64_t>& recv_counts,
-    const c10::optional<Tensor>& send_index,
-    const c10::optional<Tensor>& recv_index, int64_t out_size, int64_t fan) {
-  const auto sp = mx8_seg_plan(send_counts, rows, after);
-  const auto rp = mx8_seg_plan(recv_counts, rows, after);
-  auto q = mx8_quantize_segments(in, rows, after, send_counts, send_index);
-  auto bopts = in.options().dtype(at::kByte);
-  auto stg_pay = at::empty({rp.total_groups * 32}, bopts);
-  auto stg_sc = at::empty({rp.total_groups}, bopts);
-  mx8_exchange(tr, {q.first, q.second, sp.goffs(), sp.groups},
-               {stg_pay, stg_sc, rp.goffs(), rp.groups});
-  if (!recv_index.has_value()) {
-    return mx8_dequantize_segments(stg_pay, stg_sc, rows, after, recv_counts,
-                                   c10::nullopt, in.scalar_type());
-  }
-  return mx8_dequantize_combine(stg_pay, stg_sc, after, recv_counts,
-                                *recv_index, out_size, fan, in.scalar_type());
-}
-
-// ---- the gated top-k tail: weights on either side of the wire --------------
-//
-// Rule of the weighted sum (normative; mx8_dequantize_combine_weighted_kernel
-// matches it bit for bit): with w [R] fp32 next to the values,
-//   acc = fl(w * v)(tab[s][0]), or +0.0 when that entry is -1;
-//   acc = acc + fl(w * v)(tab[s][j]) for j = 1..fan-1, -1 skipped;
-// the product rounded to fp32 before the add (two torch ops, no FMA).
-Tensor weighted_table_sum(const Tensor& v, const Tensor& w,
-                          const Tensor& tab) {
-  const int64_t out_size = tab.size(0), fan = tab.size(1);
-  auto acc = at::zeros({out_size, v.size(1)}, v.options());
-  if (v.size(0) == 0) return acc;
-  for (int64_t j = 0; j < fan; ++j) {
-    auto col = tab.select(1, j);
-    auto ok = col.ge(0).unsqueeze(1);
-    auto src = col.clamp_min(0);
-    auto term = w.index_select(0, src).unsqueeze(1) * v.index_select(0, src);
-    acc = at::where(ok, j == 0 ? term : acc + term, acc);
-  }
-  return acc;
-}
-
-Tensor table_view(const Tensor& flat, int64_t out_size, int64_t fan) {
-  return flat.narrow(0, 0, out_size * fan).view({out_size, fan});
-}
-
-// mx8_dequantize_combine with weights (fp32 [R], one per received slice).
-Tensor mx8_dequantize_combine_weighted(
-    const Tensor& pay, const Tensor& sc, int64_t after,
-    const std::vector<int64_t>& counts, const Tensor& index,
-    const Tensor& weights, int64_t out_size, int64_t fan,
-    at::ScalarType dtype, const c10::optional<Tensor>& out_opt = c10::nullopt) {
-  const int dt = mx8_dtype_code(dtype);
-  const auto pl = mx8_seg_plan(counts, 1, after);
-  if (pay.is_cuda()) {
-    auto out = out_or_empty(out_opt, {out_size, after},
-                            pay.options().dtype(dtype));
-    auto tabs = mx8_combine_tables_weighted(
-        index, mx8_slice_offsets(pl, after, index.options()), weights,
-        out_size, fan);
-    launch_mx8_dequantize_combine_weighted(
-        pay.data_ptr(), sc.data_ptr(), tabs.first.data_ptr<int64_t>(),
-        tabs.second.data_ptr<float>(), out.data_ptr(), out_size, (int)fan,
-        after, dt, current_gpu_stream(pay));
-    return out;
-  }
-  auto table = mx8_combine_table(index, at::arange(pl.slices, index.options()),
-                                 out_size, fan);
-  auto res = weighted_table_sum(mx8_segment_values(pay, sc, pl, after),
-                                weights, table_view(table, out_size, fan))
-                 .to(dtype);
-  return out_opt.has_value() ? out_opt->copy_(res) : res;
-}
-
-// mx8_quantize_segments for rows == 1 with weights (fp32 [sum(counts)]):
-// stream slice i is fl32(w_i * f32(in[order_i])) (in[i] without an order),
-// an order entry outside [0, S) reading as zeros; segment p is mx8_quantize
-// of its fp32 products. The product never rounds to in's dtype.
-std::pair<Tensor, Tensor> mx8_quantize_segments_weighted(
-    const Tensor& in, int64_t after, const std::vector<int64_t>& counts,
-    const c10::optional<Tensor>& order, const Tensor& weights,
-    const c10::optional<Tensor>& payload_out = c10::nullopt,
-    const c10::optional<Tensor>& scales_out = c10::nullopt) {
-  const int dt = mx8_dtype_code(in.scalar_type());
-  const auto pl = mx8_seg_plan(counts, 1, after);
-  const int64_t S = after > 0 ? in.numel() / after : 0;
-  auto bopts = in.options().dtype(at::kByte);
-  auto pay = payload_out.has_value()
-                 ? payload_out->narrow(0, 0, pl.total_groups * 32)
-                 : at::empty({pl.total_groups * 32}, bopts);
-  auto sc = scales_out.has_value() ? scales_out->narrow(0, 0, pl.total_groups)
-                                   : at::empty({pl.total_groups}, bopts);
-  if (pl.total_groups == 0) return {pay, sc};
-  if (in.is_cuda()) {
-    launch_mx8_quantize_segments_weighted(
-        in.data_ptr(),
-        order.has_value() ? order->data_ptr<int64_t>() : nullptr,
-        weights.data_ptr<float>(), pay.data_ptr(), sc.data_ptr(),
-        pl.segs.data(), (int)pl.segs.size(), S, after, dt,
-        current_gpu_stream(in));
-    return {pay, sc};
-  }
-  auto xs = in.view({S, after}).to(at::kFloat);
-  if (order.has_value()) {
-    auto ok = order->ge(0).logical_and(order->lt(S)).unsqueeze(1);
-    xs = at::where(ok, xs.index_select(0, order->clamp(0, S > 0 ? S - 1 : 0)),
-                   at::zeros({}, xs.options()));
-  }
-  auto prod = weights.unsqueeze(1) * xs;
-  for (size_t p = 0; p < counts.size(); ++p) {
-    if (pl.groups[p] == 0) continue;
-    auto q = mx8_quantize(
-        prod.narrow(0, pl.segs[p].displ, counts[p]).contiguous().view({-1}));
-    pay.narrow(0, pl.segs[p].goff * 32, pl.groups[p] * 32).copy_(q.first);
-    sc.narrow(0, pl.segs[p].goff, pl.groups[p]).copy_(q.second);
-  }
-  return {pay, sc};
 }
 
 // The gate gradient of the gated tail: gw[i] = sum_a dq(received slice i)[a] *
@@ -1639,44 +1516,54 @@ Tensor mx8_dequantize_rowdot(const Tensor& pay, const Tensor& sc,
   return out_opt.has_value() ? out_opt->copy_(res) : res;
 }
 
-// mx8_alltoall_pairwise_indexed for rows == 1 with weights on either side:
-// the head scales stream slice i by send_weights[i] before it quantizes, the
-// tail scales received slice i by recv_weights[i] while it sums (recv_weights
-// needs recv_index). With `wire` the received payload and scale bytes are
-// handed out as well: the gate gradient is computed from them.
-Tensor mx8_alltoall_pairwise_weighted(
-    Transport& tr, const Tensor& in, int64_t after,
+// The pairwise all-to-all of the family: `in` is this rank's contiguous
+// tensor seen as [rows, S, after]. The fused head gathers slices through
+// send_index while it quantizes segment p (what rank p receives) in groups of
+// 32 that start at the segment; payload and scales travel as two contiguous
+// pieces per peer in ONE grouped call, their sizes 32*G and G computed from
+// the counts both ends know; the fused tail dequantizes the received
+// segments, the own one included, straight into the result. No index_select
+// pass on either side; every value is quantized exactly once. Both transports
+// skip zero-length pieces on both ends of a pair, and so does this: an empty
+// segment is not listed at all.
+//
+// send_index may repeat slices (the quantize kernel never needed an
+// injective index). The tail is picked by recv_index and fan:
+//   no recv_index        the segments tail into [rows, R, after];
+//   recv_index, fan == 0 the segments tail, scattering slices through the
+//                        permutation recv_index while it writes;
+//   recv_index, fan >= 1 mx8_dequantize_combine into out_size slices
+//                        (rows == 1), weighted with recv_weights.
+// With send_weights (rows == 1) the head scales stream slice i by
+// send_weights[i] before it quantizes. With `wire` the received payload and
+// scale bytes are handed out as well: the gate gradient is computed from
+// them.
+Tensor mx8_alltoall_pairwise(
+    Transport& tr, const Tensor& in, int64_t rows, int64_t after,
     const std::vector<int64_t>& send_counts,
     const std::vector<int64_t>& recv_counts,
     const c10::optional<Tensor>& send_index,
-    const c10::optional<Tensor>& send_weights,
-    const c10::optional<Tensor>& recv_index,
-    const c10::optional<Tensor>& recv_weights, int64_t out_size, int64_t fan,
-    std::pair<Tensor, Tensor>* wire) {
-  const auto sp = mx8_seg_plan(send_counts, 1, after);
-  const auto rp = mx8_seg_plan(recv_counts, 1, after);
-  auto q = send_weights.has_value()
-               ? mx8_quantize_segments_weighted(in, after, send_counts,
-                                                send_index, *send_weights)
-               : mx8_quantize_segments(in, 1, after, send_counts, send_index);
+    const c10::optional<Tensor>& recv_index, int64_t out_size = 0,
+    int64_t fan = 0, const c10::optional<Tensor>& send_weights = c10::nullopt,
+    const c10::optional<Tensor>& recv_weights = c10::nullopt,
+    std::pair<Tensor, Tensor>* wire = nullptr) {
+  const auto sp = mx8_seg_plan(send_counts, rows, after);
+  const auto rp = mx8_seg_plan(recv_counts, rows, after);
+  auto q = mx8_quantize_segments(in, rows, after, send_counts, send_index,
+                                 c10::nullopt, c10::nullopt, send_weights);
   auto bopts = in.options().dtype(at::kByte);
   auto stg_pay = at::empty({rp.total_groups * 32}, bopts);
   auto stg_sc = at::empty({rp.total_groups}, bopts);
   mx8_exchange(tr, {q.first, q.second, sp.goffs(), sp.groups},
                {stg_pay, stg_sc, rp.goffs(), rp.groups});
   if (wire != nullptr) *wire = {stg_pay, stg_sc};
-  if (!recv_index.has_value()) {
-    return mx8_dequantize_segments(stg_pay, stg_sc, 1, after, recv_counts,
-                                   c10::nullopt, in.scalar_type());
+  if (!recv_index.has_value() || fan == 0) {
+    return mx8_dequantize_segments(stg_pay, stg_sc, rows, after, recv_counts,
+                                   recv_index, in.scalar_type());
   }
-  if (!recv_weights.has_value()) {
-    return mx8_dequantize_combine(stg_pay, stg_sc, after, recv_counts,
-                                  *recv_index, out_size, fan,
-                                  in.scalar_type());
-  }
-  return mx8_dequantize_combine_weighted(stg_pay, stg_sc, after, recv_counts,
-                                         *recv_index, *recv_weights, out_size,
-                                         fan, in.scalar_type());
+  return mx8_dequantize_combine(stg_pay, stg_sc, after, recv_counts,
+                                *recv_index, recv_weights, out_size, fan,
+                                in.scalar_type());
 }
 
 // The mxfp8 sibling of hierarchical_allreduce: quantize once, exchange each
@@ -3218,28 +3105,104 @@ struct AlltoallPairwiseCompressedBackward : public M4ANode {
   c10::optional<Tensor> send_order, recv_order;
 };
 
-// Shape, dtype and device always; the permutation property on the CPU, and
-// on the GPU only under the desync detector's debug mode (it costs a sync).
+// The counts of a pairwise exchange: recv_counts exchanged when empty (my
+// recv from j = j's send to me), both checked, their sums returned.
+void resolve_pairwise_counts(const char* who, Transport& tr0,
+                             const std::string& group_name,
+                             std::vector<int64_t>& send_counts,
+                             std::vector<int64_t>& recv_counts,
+                             int64_t* s_total, int64_t* r_total) {
+  const int P = tr0.size();
+  TORCH_CHECK((int)send_counts.size() == P, who,
+              ": send_counts must have world_size entries");
+  if (recv_counts.empty() && P > 1) {
+    auto mat = host_allgather_int64_vec(group_name, send_counts);
+    recv_counts.resize(P);
+    const int me = tr0.rank();
+    for (int j = 0; j < P; ++j) recv_counts[j] = mat[(int64_t)j * P + me];
+  }
+  if (P == 1 && recv_counts.empty()) recv_counts = send_counts;
+  TORCH_CHECK((int)recv_counts.size() == P, who,
+              ": recv_counts must have world_size entries");
+  for (int64_t c : send_counts) {
+    TORCH_CHECK(c >= 0, who, ": negative send count ", c);
+    *s_total += c;
+  }
+  for (int64_t c : recv_counts) {
+    TORCH_CHECK(c >= 0, who, ": negative recv count ", c);
+    *r_total += c;
+  }
+}
+
+// Shape, dtype and device of an optional order, index or weight tensor of
+// one entry per stream slice: int64, or for a weight fp32 or the input's.
+void check_pairwise_slices(const char* who, const char* which,
+                           const c10::optional<Tensor>& t, int64_t len,
+                           const Tensor& input, bool weight = false) {
+  if (!t.has_value()) return;
+  TORCH_CHECK(t->dim() == 1 && t->numel() == len, who, ": ", which,
+              " must be a 1-D tensor of length ", len,
+              " (the sum of its counts), got shape ", t->sizes());
+  if (weight) {
+    TORCH_CHECK(t->scalar_type() == at::kFloat ||
+                    t->scalar_type() == input.scalar_type(),
+                who, ": ", which, " must be float32 or the tensor's dtype ",
+                input.scalar_type(), ", got ", t->scalar_type());
+  } else {
+    TORCH_CHECK(t->scalar_type() == at::kLong, who, ": ", which,
+                " must be an int64 tensor, got ", t->scalar_type());
+  }
+  TORCH_CHECK(t->device() == input.device(), who, ": ", which,
+              " must be on the tensor's device ", input.device(), ", got ",
+              t->device());
+}
+
+// An optional order, index or weight tensor follows the input through the
+// stager; the weights travel nowhere and are cast to fp32 here.
+c10::optional<Tensor> stage_pairwise_slices(const DeviceStager& stager,
+                                            const c10::optional<Tensor>& t,
+                                            bool weight = false) {
+  c10::optional<Tensor> o;
+  if (t.has_value()) {
+    auto c = stager.to_comm(*t).contiguous().variable_data();
+    o = weight ? c.to(at::kFloat) : c;
+  }
+  return o;
+}
+
+// check_pairwise_slices always; the permutation property on the CPU, and on
+// the GPU only under the desync detector's debug mode (it costs a sync).
 void check_pairwise_order(const char* which,
                           const c10::optional<Tensor>& order, int64_t len,
                           const Tensor& input) {
-  if (!order.has_value()) return;
-  const Tensor& o = *order;
-  TORCH_CHECK(o.dim() == 1 && o.numel() == len,
-              "AlltoallPairwiseCompressed: ", which, " must be a 1-D tensor "
-              "of length ", len, " (the sum of its counts), got shape ",
-              o.sizes());
-  TORCH_CHECK(o.scalar_type() == at::kLong,
-              "AlltoallPairwiseCompressed: ", which, " must be an int64 "
-              "tensor, got ", o.scalar_type());
-  TORCH_CHECK(o.device() == input.device(),
-              "AlltoallPairwiseCompressed: ", which, " must be on the "
-              "tensor's device ", input.device(), ", got ", o.device());
-  if (len > 0 && (!o.is_cuda() || config().debug_collectives)) {
-    const bool perm = std::get<0>(o.sort()).equal(
-        at::arange(len, o.options()));
+  check_pairwise_slices("AlltoallPairwiseCompressed", which, order, len,
+                        input);
+  if (order.has_value() && len > 0 &&
+      (!order->is_cuda() || config().debug_collectives)) {
+    const bool perm = std::get<0>(order->sort()).equal(
+        at::arange(len, order->options()));
     TORCH_CHECK(perm, "AlltoallPairwiseCompressed: ", which, " must be a "
                 "permutation of 0..", len - 1);
+  }
+}
+
+// check_pairwise_slices always; range and the repeat bound on the CPU, and
+// on the GPU only under the desync detector's debug mode (they cost a sync).
+void check_pairwise_index(const char* who, const char* which,
+                          const c10::optional<Tensor>& index, int64_t len,
+                          int64_t size, int64_t max_repeat,
+                          const Tensor& input) {
+  check_pairwise_slices(who, which, index, len, input);
+  if (index.has_value() && len > 0 &&
+      (!index->is_cuda() || config().debug_collectives)) {
+    const Tensor& o = *index;
+    TORCH_CHECK(o.min().item<int64_t>() >= 0 && o.max().item<int64_t>() < size,
+                who, ": ", which, " entries must "
+                "lie in [0, ", size, ")");
+    const int64_t most = at::bincount(o).max().item<int64_t>();
+    TORCH_CHECK(most <= max_repeat,
+                who, ": a slice occurs ", most,
+                " times in ", which, ", more than max_repeat = ", max_repeat);
   }
 }
 } // namespace
@@ -3248,33 +3211,12 @@ Tensor Communicator::AlltoallPairwiseCompressed(
     const Tensor& input, int64_t axis, std::vector<int64_t> send_counts,
     std::vector<int64_t> recv_counts, c10::optional<Tensor> send_order,
     c10::optional<Tensor> recv_order) {
-  check_mx8_input("AlltoallPairwiseCompressed", input);
+  const char* who = "AlltoallPairwiseCompressed";
+  check_mx8_input(who, input);
   axis = at::maybe_wrap_dim(axis, input.dim());
-  auto& tr0 = cpu_tr();
-  const int P = tr0.size();
-  TORCH_CHECK((int)send_counts.size() == P,
-              "AlltoallPairwiseCompressed: send_counts must have world_size "
-              "entries");
-  if (recv_counts.empty() && P > 1) {
-    // exchange the count matrix; my recv from j = j's send to me
-    auto mat = host_allgather_int64_vec(group_name_, send_counts);
-    recv_counts.resize(P);
-    const int me = tr0.rank();
-    for (int j = 0; j < P; ++j) recv_counts[j] = mat[(int64_t)j * P + me];
-  }
-  if (P == 1 && recv_counts.empty()) recv_counts = send_counts;
-  TORCH_CHECK((int)recv_counts.size() == P,
-              "AlltoallPairwiseCompressed: recv_counts must have world_size "
-              "entries");
   int64_t s_total = 0, r_total = 0;
-  for (int64_t c : send_counts) {
-    TORCH_CHECK(c >= 0, "AlltoallPairwiseCompressed: negative send count ", c);
-    s_total += c;
-  }
-  for (int64_t c : recv_counts) {
-    TORCH_CHECK(c >= 0, "AlltoallPairwiseCompressed: negative recv count ", c);
-    r_total += c;
-  }
+  resolve_pairwise_counts(who, cpu_tr(), group_name_, send_counts, recv_counts,
+                          &s_total, &r_total);
   TORCH_CHECK(input.size(axis) == s_total,
               "AlltoallPairwiseCompressed: sum of send_counts (", s_total,
               ") must equal the axis size (", input.size(axis), ")");
@@ -3287,14 +3229,8 @@ Tensor Communicator::AlltoallPairwiseCompressed(
   };
   auto body = [&](Transport& tr, const Tensor& in,
                   const DeviceStager& stager) -> Tensor {
-    // the order tensors follow the input through the stager
-    c10::optional<Tensor> so, ro;
-    if (send_order.has_value()) {
-      so = stager.to_comm(*send_order).contiguous().variable_data();
-    }
-    if (recv_order.has_value()) {
-      ro = stager.to_comm(*recv_order).contiguous().variable_data();
-    }
+    const auto so = stage_pairwise_slices(stager, send_order);
+    const auto ro = stage_pairwise_slices(stager, recv_order);
     auto outsizes = in.sizes().vec();
     outsizes[axis] = r_total;
     // World of one: the result is the exact permutation, under the rule of
@@ -3361,140 +3297,7 @@ struct AlltoallPairwiseCompressedIndexedBackward : public M4ANode {
   int64_t in_size, max_repeat;
 };
 
-// Shape, dtype and device always; range and the repeat bound on the CPU,
-// and on the GPU only under the desync detector's debug mode (they cost a
-// sync).
-void check_pairwise_index(const char* who, const char* which,
-                          const c10::optional<Tensor>& index, int64_t len,
-                          int64_t size, int64_t max_repeat,
-                          const Tensor& input) {
-  if (!index.has_value()) return;
-  const Tensor& o = *index;
-  TORCH_CHECK(o.dim() == 1 && o.numel() == len,
-              who, ": ", which, " must be a 1-D "
-              "tensor of length ", len, " (the sum of its counts), got shape ",
-              o.sizes());
-  TORCH_CHECK(o.scalar_type() == at::kLong,
-              who, ": ", which, " must be an "
-              "int64 tensor, got ", o.scalar_type());
-  TORCH_CHECK(o.device() == input.device(),
-              who, ": ", which, " must be on the "
-              "tensor's device ", input.device(), ", got ", o.device());
-  if (len > 0 && (!o.is_cuda() || config().debug_collectives)) {
-    TORCH_CHECK(o.min().item<int64_t>() >= 0 && o.max().item<int64_t>() < size,
-                who, ": ", which, " entries must "
-                "lie in [0, ", size, ")");
-    const int64_t most = at::bincount(o).max().item<int64_t>();
-    TORCH_CHECK(most <= max_repeat,
-                who, ": a slice occurs ", most,
-                " times in ", which, ", more than max_repeat = ", max_repeat);
-  }
-}
-
-// The counts of a pairwise exchange: recv_counts exchanged when empty (my
-// recv from j = j's send to me), both checked, their sums returned.
-void resolve_pairwise_counts(const char* who, Transport& tr0,
-                             const std::string& group_name,
-                             std::vector<int64_t>& send_counts,
-                             std::vector<int64_t>& recv_counts,
-                             int64_t* s_total, int64_t* r_total) {
-  const int P = tr0.size();
-  TORCH_CHECK((int)send_counts.size() == P, who,
-              ": send_counts must have world_size entries");
-  if (recv_counts.empty() && P > 1) {
-    auto mat = host_allgather_int64_vec(group_name, send_counts);
-    recv_counts.resize(P);
-    const int me = tr0.rank();
-    for (int j = 0; j < P; ++j) recv_counts[j] = mat[(int64_t)j * P + me];
-  }
-  if (P == 1 && recv_counts.empty()) recv_counts = send_counts;
-  TORCH_CHECK((int)recv_counts.size() == P, who,
-              ": recv_counts must have world_size entries");
-  for (int64_t c : send_counts) {
-    TORCH_CHECK(c >= 0, who, ": negative send count ", c);
-    *s_total += c;
-  }
-  for (int64_t c : recv_counts) {
-    TORCH_CHECK(c >= 0, who, ": negative recv count ", c);
-    *r_total += c;
-  }
-}
 } // namespace
-
-Tensor Communicator::AlltoallPairwiseCompressedIndexed(
-    const Tensor& input, int64_t axis, std::vector<int64_t> send_counts,
-    std::vector<int64_t> recv_counts, c10::optional<Tensor> send_index,
-    c10::optional<Tensor> recv_index, c10::optional<int64_t> out_size,
-    int64_t max_repeat) {
-  const char* who = "AlltoallPairwiseCompressedIndexed";
-  check_mx8_input(who, input);
-  axis = at::maybe_wrap_dim(axis, input.dim());
-  int64_t s_total = 0, r_total = 0;
-  resolve_pairwise_counts(who, cpu_tr(), group_name_, send_counts, recv_counts,
-                          &s_total, &r_total);
-  TORCH_CHECK(max_repeat >= 1, who, ": max_repeat must be >= 1, got ",
-              max_repeat);
-  const int64_t in_size = input.size(axis);
-  TORCH_CHECK(send_index.has_value() || in_size == s_total, who,
-              ": without a send_index the sum of send_counts (", s_total,
-              ") must equal the axis size (", in_size, ")");
-  TORCH_CHECK(!recv_index.has_value() || out_size.has_value(), who,
-              ": out_size is required with a recv_index");
-  TORCH_CHECK(!out_size.has_value() || *out_size >= 0, who,
-              ": out_size must be >= 0, got ", out_size.value_or(0));
-  const auto g0 = axis_geom(input, axis);
-  TORCH_CHECK(!recv_index.has_value() || g0.before == 1, who,
-              ": with a recv_index every dimension before the axis must have "
-              "size 1 (token tensors are [N, D]), got shape ", input.sizes(),
-              " with axis ", axis);
-  const int64_t n_out = recv_index.has_value() ? *out_size : r_total;
-  check_pairwise_index(who, "send_index", send_index, s_total, in_size,
-                       max_repeat, input);
-  check_pairwise_index(who, "recv_index", recv_index, r_total, n_out,
-                       max_repeat, input);
-
-  auto make_grad_fn = [&](auto comm) {
-    return make_node<AlltoallPairwiseCompressedIndexedBackward>(
-        comm, axis, send_counts, recv_counts, send_index, recv_index, in_size,
-        max_repeat);
-  };
-  auto body = [&](Transport& tr, const Tensor& in,
-                  const DeviceStager& stager) -> Tensor {
-    // the index tensors follow the input through the stager
-    c10::optional<Tensor> si, ri;
-    if (send_index.has_value()) {
-      si = stager.to_comm(*send_index).contiguous().variable_data();
-    }
-    if (recv_index.has_value()) {
-      ri = stager.to_comm(*recv_index).contiguous().variable_data();
-    }
-    auto outsizes = in.sizes().vec();
-    outsizes[axis] = n_out;
-    const auto g = axis_geom(in, axis);
-    // World of one: the exact, uncompressed result — the gather, then the
-    // ordered fp32 table sum on the values themselves, then the cast.
-    // force_full_path runs the whole pipeline on either device.
-    if (w1_shortcut(tr)) {
-      auto y = si.has_value() ? in.index_select(axis, *si) : fast_clone(in);
-      if (!ri.has_value()) return y;
-      auto table = mx8_combine_table(*ri, at::arange(r_total, ri->options()),
-                                     n_out, max_repeat);
-      return ordered_table_sum(
-                 y.view({r_total, g.after}).to(at::kFloat),
-                 table.narrow(0, 0, n_out * max_repeat)
-                     .view({n_out, max_repeat}))
-          .to(in.scalar_type())
-          .view(outsizes);
-    }
-    debug_check_axis_collective(group_name_, who, in, {axis}, {axis});
-    if (g.before * g.after == 0) return at::zeros(outsizes, in.options());
-    return mx8_alltoall_pairwise_indexed(tr, in, g.before, g.after,
-                                         send_counts, recv_counts, si, ri,
-                                         n_out, max_repeat)
-        .view(outsizes);
-  };
-  return collective_frame(*this, input, make_grad_fn, body);
-}
 
 // ---------------------------------------------------------------------------
 // AlltoallPairwiseCompressedWeighted (MI355X extension; not in the reference
@@ -3569,36 +3372,21 @@ struct AlltoallPairwiseCompressedWeightedBackward : public M4ANode {
   Tensor values;             // world of one: the [R, after] values instead
 };
 
-// 1-D, length, dtype (fp32 or the input's) and device of a weight tensor.
-void check_pairwise_weights(const char* who, const char* which,
-                            const c10::optional<Tensor>& w, int64_t len,
-                            const Tensor& input) {
-  if (!w.has_value()) return;
-  TORCH_CHECK(w->dim() == 1 && w->numel() == len, who, ": ", which,
-              " must be a 1-D tensor of length ", len,
-              " (the sum of its counts), got shape ", w->sizes());
-  TORCH_CHECK(w->scalar_type() == at::kFloat ||
-                  w->scalar_type() == input.scalar_type(),
-              who, ": ", which, " must be float32 or the tensor's dtype ",
-              input.scalar_type(), ", got ", w->scalar_type());
-  TORCH_CHECK(w->device() == input.device(), who, ": ", which,
-              " must be on the tensor's device ", input.device(), ", got ",
-              w->device());
-}
-} // namespace
-
-Tensor Communicator::AlltoallPairwiseCompressedWeighted(
-    const Tensor& input, int64_t axis, std::vector<int64_t> send_counts,
-    std::vector<int64_t> recv_counts, c10::optional<Tensor> send_index,
-    c10::optional<Tensor> send_weights, c10::optional<Tensor> recv_index,
-    c10::optional<Tensor> recv_weights, c10::optional<int64_t> out_size,
-    int64_t max_repeat) {
-  const char* who = "AlltoallPairwiseCompressedWeighted";
-  if (!send_weights.has_value() && !recv_weights.has_value()) {
-    return AlltoallPairwiseCompressedIndexed(
-        input, axis, std::move(send_counts), std::move(recv_counts),
-        std::move(send_index), std::move(recv_index), out_size, max_repeat);
-  }
+// The Indexed and the Weighted front-end. With a weight on either side the
+// op is the Weighted one (its name in messages, its node: two differentiable
+// inputs, and the node receives what the body saves for it, so the frame is
+// collective_frame written out); without one it is the Indexed op.
+Tensor pairwise_indexed(Communicator& comm, const Tensor& input, int64_t axis,
+                        std::vector<int64_t> send_counts,
+                        std::vector<int64_t> recv_counts,
+                        const c10::optional<Tensor>& send_index,
+                        const c10::optional<Tensor>& send_weights,
+                        const c10::optional<Tensor>& recv_index,
+                        const c10::optional<Tensor>& recv_weights,
+                        c10::optional<int64_t> out_size, int64_t max_repeat) {
+  const bool weighted = send_weights.has_value() || recv_weights.has_value();
+  const char* who = weighted ? "AlltoallPairwiseCompressedWeighted"
+                             : "AlltoallPairwiseCompressedIndexed";
   check_mx8_input(who, input);
   axis = at::maybe_wrap_dim(axis, input.dim());
   TORCH_CHECK(!recv_weights.has_value() || recv_index.has_value(), who,
@@ -3607,8 +3395,8 @@ Tensor Communicator::AlltoallPairwiseCompressedWeighted(
               ": send_weights are not differentiable (they exist to be the "
               "adjoint of recv_weights); detach them");
   int64_t s_total = 0, r_total = 0;
-  resolve_pairwise_counts(who, cpu_tr(), group_name_, send_counts, recv_counts,
-                          &s_total, &r_total);
+  resolve_pairwise_counts(who, comm.cpu_tr(), comm.group_name(), send_counts,
+                          recv_counts, &s_total, &r_total);
   TORCH_CHECK(max_repeat >= 1, who, ": max_repeat must be >= 1, got ",
               max_repeat);
   const int64_t in_size = input.size(axis);
@@ -3619,31 +3407,42 @@ Tensor Communicator::AlltoallPairwiseCompressedWeighted(
               ": out_size is required with a recv_index");
   TORCH_CHECK(!out_size.has_value() || *out_size >= 0, who,
               ": out_size must be >= 0, got ", out_size.value_or(0));
-  const auto g0 = axis_geom(input, axis);
-  TORCH_CHECK(g0.before == 1, who,
-              ": with weights every dimension before the axis must have size "
-              "1 (token tensors are [N, D]), got shape ", input.sizes(),
-              " with axis ", axis);
+  const auto g = axis_geom(input, axis);
+  // the combine tail and the weighted head are rows == 1 kernels
+  TORCH_CHECK(!(weighted || recv_index.has_value()) || g.before == 1, who,
+              ": with ", weighted ? "weights" : "a recv_index",
+              " every dimension before the axis must have size 1 (token "
+              "tensors are [N, D]), got shape ", input.sizes(), " with axis ",
+              axis);
   const int64_t n_out = recv_index.has_value() ? *out_size : r_total;
   check_pairwise_index(who, "send_index", send_index, s_total, in_size,
                        max_repeat, input);
   check_pairwise_index(who, "recv_index", recv_index, r_total, n_out,
                        max_repeat, input);
-  check_pairwise_weights(who, "send_weights", send_weights, s_total, input);
-  check_pairwise_weights(who, "recv_weights", recv_weights, r_total, input);
+  check_pairwise_slices(who, "send_weights", send_weights, s_total, input,
+                        /*weight=*/true);
+  check_pairwise_slices(who, "recv_weights", recv_weights, r_total, input,
+                        /*weight=*/true);
 
-  // collective_frame written out: two differentiable inputs, and the node
-  // receives what the body saves for it
   const Tensor rw_in = recv_weights.value_or(Tensor());
+  const auto self =
+      c10::intrusive_ptr<Communicator>::unsafe_reclaim_from_nonowning(&comm);
+  std::shared_ptr<Node> grad_fn;
   std::shared_ptr<AlltoallPairwiseCompressedWeightedBackward> node;
-  if (torch::autograd::compute_requires_grad(input, rw_in)) {
-    node = make_node<AlltoallPairwiseCompressedWeightedBackward>(
-        c10::intrusive_ptr<Communicator>::unsafe_reclaim_from_nonowning(this));
+  if (!weighted) {
+    if (torch::autograd::compute_requires_grad(input)) {
+      grad_fn = make_node<AlltoallPairwiseCompressedIndexedBackward>(
+          self, axis, send_counts, recv_counts, send_index, recv_index,
+          in_size, max_repeat);
+      grad_fn->set_next_edges(torch::autograd::collect_next_edges(input));
+    }
+  } else if (torch::autograd::compute_requires_grad(input, rw_in)) {
+    node = make_node<AlltoallPairwiseCompressedWeightedBackward>(self);
     node->set_next_edges(torch::autograd::collect_next_edges(input, rw_in));
     node->axis = axis;
     node->in_size = in_size;
     node->out_size = n_out;
-    node->after = g0.after;
+    node->after = g.after;
     node->max_repeat = max_repeat;
     node->send = send_counts;
     node->recv = recv_counts;
@@ -3654,56 +3453,50 @@ Tensor Communicator::AlltoallPairwiseCompressedWeighted(
       node->recv_weights = rw_in.detach();
       node->weight_dtype = rw_in.scalar_type();
     }
+    grad_fn = node;
   }
   // the wire bytes are kept only for a weight that wants its gradient
   const bool need_gw = node && rw_in.requires_grad();
   auto body = [&](Transport& tr, const Tensor& in,
                   const DeviceStager& stager) -> Tensor {
-    // index and weight tensors follow the input through the stager; the
-    // weights travel nowhere and are cast to fp32 here
-    auto staged = [&](const c10::optional<Tensor>& t, bool weight) {
-      c10::optional<Tensor> o;
-      if (t.has_value()) {
-        auto c = stager.to_comm(*t).contiguous().variable_data();
-        o = weight ? c.to(at::kFloat) : c;
-      }
-      return o;
-    };
-    const auto si = staged(send_index, false), ri = staged(recv_index, false);
-    const auto sw = staged(send_weights, true), rw = staged(recv_weights, true);
+    const auto si = stage_pairwise_slices(stager, send_index);
+    const auto ri = stage_pairwise_slices(stager, recv_index);
+    const auto sw = stage_pairwise_slices(stager, send_weights, true);
+    const auto rw = stage_pairwise_slices(stager, recv_weights, true);
     if (node) node->recv_index_comm = ri;
     auto outsizes = in.sizes().vec();
     outsizes[axis] = n_out;
-    const int64_t after = g0.after;
     // World of one: the exact, uncompressed result — gather, fp32 weighting,
-    // ordered table sum, cast. force_full_path runs the whole pipeline on
-    // either device.
+    // ordered table sum on the values themselves, cast. force_full_path runs
+    // the whole pipeline on either device.
     if (w1_shortcut(tr)) {
       auto y = si.has_value() ? in.index_select(axis, *si) : in;
-      auto yv = y.view({r_total, after});
+      // the one result that is the input's values: any `before`, a copy
+      if (!ri.has_value() && !sw.has_value()) {
+        return si.has_value() ? y : fast_clone(in);
+      }
+      auto yv = y.view({r_total, g.after});
       if (sw.has_value()) yv = sw->unsqueeze(1) * yv.to(at::kFloat);
       // the input's own storage is not kept
       if (need_gw) node->values = yv.is_alias_of(in) ? yv.clone() : yv;
       if (!ri.has_value()) return yv.to(in.scalar_type()).view(outsizes);
       auto table = mx8_combine_table(*ri, at::arange(r_total, ri->options()),
                                      n_out, max_repeat);
-      auto tab = table_view(table, n_out, max_repeat);
-      auto yf = yv.to(at::kFloat);
-      return (rw.has_value() ? weighted_table_sum(yf, *rw, tab)
-                             : ordered_table_sum(yf, tab))
+      return ordered_table_sum(yv.to(at::kFloat),
+                               table_view(table, n_out, max_repeat), rw)
           .to(in.scalar_type())
           .view(outsizes);
     }
-    debug_check_axis_collective(group_name_, who, in, {axis}, {axis});
-    if (after == 0) {
+    debug_check_axis_collective(comm.group_name(), who, in, {axis}, {axis});
+    if (g.before * g.after == 0) {
       // nothing to send; the weights' gradient is a dot over no elements
       if (need_gw) node->values = at::zeros({r_total, 0}, in.options());
       return at::zeros(outsizes, in.options());
     }
     std::pair<Tensor, Tensor> wire;
-    auto out = mx8_alltoall_pairwise_weighted(
-        tr, in, after, send_counts, recv_counts, si, sw, ri, rw, n_out,
-        max_repeat, need_gw ? &wire : nullptr);
+    auto out = mx8_alltoall_pairwise(tr, in, g.before, g.after, send_counts,
+                                     recv_counts, si, ri, n_out, max_repeat,
+                                     sw, rw, need_gw ? &wire : nullptr);
     if (need_gw) {
       node->wire_pay = wire.first;
       node->wire_sc = wire.second;
@@ -3714,10 +3507,32 @@ Tensor Communicator::AlltoallPairwiseCompressedWeighted(
     at::AutoDispatchBelowADInplaceOrView guard;
     DeviceStager stager(input);
     auto in = stager.to_comm(input).contiguous().variable_data();
-    return stager.from_comm(body(tr_for(in), in, stager));
+    return stager.from_comm(body(comm.tr_for(in), in, stager));
   }();
-  attach_history(result, node);
+  attach_history(result, grad_fn);
   return result;
+}
+} // namespace
+
+Tensor Communicator::AlltoallPairwiseCompressedIndexed(
+    const Tensor& input, int64_t axis, std::vector<int64_t> send_counts,
+    std::vector<int64_t> recv_counts, c10::optional<Tensor> send_index,
+    c10::optional<Tensor> recv_index, c10::optional<int64_t> out_size,
+    int64_t max_repeat) {
+  return pairwise_indexed(*this, input, axis, std::move(send_counts),
+                          std::move(recv_counts), send_index, c10::nullopt,
+                          recv_index, c10::nullopt, out_size, max_repeat);
+}
+
+Tensor Communicator::AlltoallPairwiseCompressedWeighted(
+    const Tensor& input, int64_t axis, std::vector<int64_t> send_counts,
+    std::vector<int64_t> recv_counts, c10::optional<Tensor> send_index,
+    c10::optional<Tensor> send_weights, c10::optional<Tensor> recv_index,
+    c10::optional<Tensor> recv_weights, c10::optional<int64_t> out_size,
+    int64_t max_repeat) {
+  return pairwise_indexed(*this, input, axis, std::move(send_counts),
+                          std::move(recv_counts), send_index, send_weights,
+                          recv_index, recv_weights, out_size, max_repeat);
 }
 
 // ---------------------------------------------------------------------------
@@ -4352,6 +4167,32 @@ std::tuple<Tensor, Tensor> debug_mx8_quantize_segments(
   return std::make_tuple(ps.first, ps.second);
 }
 
+namespace {
+// the wire of a segment plan, as the debug bindings take it
+void check_debug_wire(const char* binding, const Tensor& payload,
+                      const Tensor& scales, const Mx8SegPlan& pl) {
+  TORCH_CHECK(payload.dim() == 1 && scales.dim() == 1 &&
+                  payload.is_contiguous() && scales.is_contiguous() &&
+                  payload.scalar_type() == at::kByte &&
+                  scales.scalar_type() == at::kByte &&
+                  payload.numel() == pl.total_groups * 32 &&
+                  scales.numel() == pl.total_groups &&
+                  payload.device() == scales.device(),
+              binding, " expects flat contiguous uint8 payload [32*sum(G)] "
+              "and scales [sum(G)]");
+}
+
+// index (int64) or weights (float32): contiguous, one per slice, on `dev`
+void check_debug_per_slice(const char* binding, const char* which,
+                           const Tensor& t, at::ScalarType dtype, int64_t len,
+                           const at::Device& dev) {
+  TORCH_CHECK(t.dim() == 1 && t.numel() == len && t.scalar_type() == dtype &&
+                  t.is_contiguous() && t.device() == dev,
+              binding, ": ", which, " must be a contiguous ", dtype,
+              " tensor of sum(counts) entries on the data's device");
+}
+} // namespace
+
 Tensor debug_mx8_dequantize_segments(const Tensor& payload,
                                      const Tensor& scales, int64_t rows,
                                      int64_t after,
@@ -4362,15 +4203,7 @@ Tensor debug_mx8_dequantize_segments(const Tensor& payload,
   TORCH_CHECK(rows >= 1 && after >= 1,
               "debug_mx8_dequantize_segments: rows and after must be >= 1");
   const auto pl = mx8_seg_plan(counts, rows, after);
-  TORCH_CHECK(payload.dim() == 1 && scales.dim() == 1 &&
-                  payload.is_contiguous() && scales.is_contiguous() &&
-                  payload.scalar_type() == at::kByte &&
-                  scales.scalar_type() == at::kByte &&
-                  payload.numel() == pl.total_groups * 32 &&
-                  scales.numel() == pl.total_groups &&
-                  payload.device() == scales.device(),
-              "debug_mx8_dequantize_segments expects flat contiguous uint8 "
-              "payload [32*sum(G)] and scales [sum(G)]");
+  check_debug_wire("debug_mx8_dequantize_segments", payload, scales, pl);
   if (order.has_value()) {
     TORCH_CHECK(order->dim() == 1 && order->numel() == pl.slices &&
                     order->scalar_type() == at::kLong &&
@@ -4402,30 +4235,21 @@ Tensor debug_mx8_dequantize_combine(const Tensor& payload,
               "debug_mx8_dequantize_combine: after and fan must be >= 1 and "
               "out_size >= 0");
   const auto pl = mx8_seg_plan(counts, 1, after);
-  TORCH_CHECK(payload.dim() == 1 && scales.dim() == 1 &&
-                  payload.is_contiguous() && scales.is_contiguous() &&
-                  payload.scalar_type() == at::kByte &&
-                  scales.scalar_type() == at::kByte &&
-                  payload.numel() == pl.total_groups * 32 &&
-                  scales.numel() == pl.total_groups &&
-                  payload.device() == scales.device(),
-              "debug_mx8_dequantize_combine expects flat contiguous uint8 "
-              "payload [32*sum(G)] and scales [sum(G)]");
+  check_debug_wire("debug_mx8_dequantize_combine", payload, scales, pl);
   TORCH_CHECK(index.dim() == 1 && index.numel() == pl.slices &&
                   index.scalar_type() == at::kLong && index.is_contiguous() &&
                   index.device() == payload.device(),
               "debug_mx8_dequantize_combine: index must be a contiguous "
               "int64 tensor of sum(counts) entries on the payload's device");
-  if (!out.has_value()) {
-    return mx8_dequantize_combine(payload, scales, after, counts, index,
-                                  out_size, fan, dtype);
+  c10::optional<Tensor> head;
+  if (out.has_value()) {
+    const int64_t total = out_size * after;
+    check_canary_out("debug_mx8_dequantize_combine", *out, total, dtype,
+                     payload.device(), "out_size*after");
+    head = out->narrow(0, 0, total).view({out_size, after});
   }
-  const int64_t total = out_size * after;
-  check_canary_out("debug_mx8_dequantize_combine", *out, total, dtype,
-                   payload.device(), "out_size*after");
-  auto head = out->narrow(0, 0, total).view({out_size, after});
   return mx8_dequantize_combine(payload, scales, after, counts, index,
-                                out_size, fan, dtype, head);
+                                c10::nullopt, out_size, fan, dtype, head);
 }
 
 Tensor debug_mx8_combine_table(const Tensor& index, int64_t after,
@@ -4437,37 +4261,12 @@ Tensor debug_mx8_combine_table(const Tensor& index, int64_t after,
                   fan >= 1,
               "debug_mx8_combine_table: index must be an int64 tensor of "
               "sum(counts) entries, out_size >= 0 and fan >= 1");
-  return mx8_combine_offsets_table(index.contiguous(), pl, after, out_size,
-                                   fan)
-      .narrow(0, 0, out_size * fan)
-      .view({out_size, fan});
+  return table_view(
+      mx8_combine_table(index.contiguous(),
+                        mx8_slice_offsets(pl, after, index.options()),
+                        out_size, fan),
+      out_size, fan);
 }
-
-namespace {
-// the wire of rows == 1 segments, as the debug bindings take it
-void check_debug_wire(const char* binding, const Tensor& payload,
-                      const Tensor& scales, const Mx8SegPlan& pl) {
-  TORCH_CHECK(payload.dim() == 1 && scales.dim() == 1 &&
-                  payload.is_contiguous() && scales.is_contiguous() &&
-                  payload.scalar_type() == at::kByte &&
-                  scales.scalar_type() == at::kByte &&
-                  payload.numel() == pl.total_groups * 32 &&
-                  scales.numel() == pl.total_groups &&
-                  payload.device() == scales.device(),
-              binding, " expects flat contiguous uint8 payload [32*sum(G)] "
-              "and scales [sum(G)]");
-}
-
-// index (int64) or weights (float32): contiguous, one per slice, on `dev`
-void check_debug_per_slice(const char* binding, const char* which,
-                           const Tensor& t, at::ScalarType dtype, int64_t len,
-                           const at::Device& dev) {
-  TORCH_CHECK(t.dim() == 1 && t.numel() == len && t.scalar_type() == dtype &&
-                  t.is_contiguous() && t.device() == dev,
-              binding, ": ", which, " must be a contiguous ", dtype,
-              " tensor of sum(counts) entries on the data's device");
-}
-} // namespace
 
 Tensor debug_mx8_dequantize_combine_weighted(
     const Tensor& payload, const Tensor& scales, int64_t after,
@@ -4490,8 +4289,8 @@ Tensor debug_mx8_dequantize_combine_weighted(
                      "out_size*after");
     head = out->narrow(0, 0, total).view({out_size, after});
   }
-  return mx8_dequantize_combine_weighted(payload, scales, after, counts, index,
-                                         weights, out_size, fan, dtype, head);
+  return mx8_dequantize_combine(payload, scales, after, counts, index, weights,
+                                out_size, fan, dtype, head);
 }
 
 std::tuple<Tensor, Tensor> debug_mx8_quantize_segments_weighted(
@@ -4520,8 +4319,8 @@ std::tuple<Tensor, Tensor> debug_mx8_quantize_segments_weighted(
     check_canary_wire(who, *payload_out, *scales_out, pl.total_groups,
                       x.device(), "32*sum(G) and sum(G)");
   }
-  auto ps = mx8_quantize_segments_weighted(x, after, counts, order, weights,
-                                           payload_out, scales_out);
+  auto ps = mx8_quantize_segments(x, 1, after, counts, order, payload_out,
+                                  scales_out, weights);
   return std::make_tuple(ps.first, ps.second);
 }
 

@@ -195,6 +195,20 @@ def test_segments_out_arguments(C):
     with pytest.raises(RuntimeError, match="float32, bfloat16 and float16"):
         C._mx8_quantize_segments(torch.ones(99, dtype=torch.int32), rows,
                                  after, counts)
+    deq = C._mx8_dequantize_segments
+    with pytest.raises(RuntimeError, match="_mx8_dequantize_segments: rows "
+                                           "and after must be >= 1"):
+        deq(pay, sc, 0, after, counts, torch.bfloat16)
+    with pytest.raises(RuntimeError, match="_mx8_dequantize_segments expects "
+                                           "flat contiguous uint8 payload "
+                                           "\\[32\\*sum\\(G\\)\\] and scales "
+                                           "\\[sum\\(G\\)\\]"):
+        deq(pay[:-32], sc, rows, after, counts, torch.bfloat16)
+    with pytest.raises(RuntimeError, match="_mx8_dequantize_segments: order "
+                                           "must be a contiguous int64 tensor "
+                                           "of sum\\(counts\\) entries on the "
+                                           "payload's device"):
+        deq(pay, sc, rows, after, counts, torch.bfloat16, order=order[:2])
 
 
 # ------------------------------ SPMD worlds -------------------------------
@@ -351,6 +365,12 @@ def test_error_checks():
         f(torch.ones(4, 4), 0, [2, 2], [4])
     with pytest.raises(RuntimeError, match="recv_counts must have world_size"):
         f(torch.ones(4, 4), 0, [4], [2, 2])
+    with pytest.raises(RuntimeError, match="AlltoallPairwiseCompressed: "
+                                           "negative send count -1"):
+        f(torch.ones(4, 4), 0, [-1], [4])
+    with pytest.raises(RuntimeError, match="AlltoallPairwiseCompressed: "
+                                           "negative recv count -2"):
+        f(torch.ones(4, 4), 0, [4], [-2])
     with pytest.raises(RuntimeError, match="sum of send_counts \\(3\\) must "
                                            "equal the axis size \\(4\\)"):
         f(torch.ones(4, 4), 0, [3], [3])

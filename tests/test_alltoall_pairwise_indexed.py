@@ -157,9 +157,33 @@ def test_error_checks():
         ("without a send_index the sum of send_counts \\(3\\) must equal the "
          "axis size \\(4\\)", (x, 0, [3], [3]), {}),
         ("float32, bfloat16 and float16", (x.double(), 0, [4], [4]), {}),
+        ("Indexed: send_counts must have world_size entries",
+         (x, 0, [2, 2], [4]), {}),
+        ("Indexed: recv_counts must have world_size entries",
+         (x, 0, [4], [2, 2]), {}),
+        ("Indexed: negative send count -1", (x, 0, [-1], [4]), {}),
+        ("Indexed: negative recv count -2", (x, 0, [4], [-2]), {}),
+        ("Indexed: max_repeat must be >= 1, got 0", (x, 0, [4], [4]),
+         dict(max_repeat=0)),
+        ("Indexed: out_size must be >= 0, got -1", (x, 0, [4], [4]),
+         dict(out_size=-1)),
     ]:
         with pytest.raises(RuntimeError, match=match):
             f(*args, **kw)
+    # the kernel binding under the combine tail
+    pay, sc = wire(8, [4], 1)
+    for match, args in [
+        ("_mx8_dequantize_combine: after and fan must be >= 1 and out_size "
+         ">= 0", (pay, sc, 8, [4], i4, 4, 0, torch.float32)),
+        ("_mx8_dequantize_combine expects flat contiguous uint8 payload "
+         "\\[32\\*sum\\(G\\)\\] and scales \\[sum\\(G\\)\\]",
+         (pay[:-1], sc, 8, [4], i4, 4, 2, torch.float32)),
+        ("_mx8_dequantize_combine: index must be a contiguous int64 tensor "
+         "of sum\\(counts\\) entries on the payload's device",
+         (pay, sc, 8, [4], i4[:3], 4, 2, torch.float32)),
+    ]:
+        with pytest.raises(RuntimeError, match=match):
+            m._C._mx8_dequantize_combine(*args)
 
 
 def _grad_case(comm, rank, world):

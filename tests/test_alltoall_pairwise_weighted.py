@@ -182,6 +182,37 @@ def test_error_checks():
               max_repeat=2)),
         ("with weights every dimension before the axis must have size 1",
          (torch.ones(2, 4, 4), 1, [4], [4]), dict(send_weights=w4)),
+        # the checks it shares with the Indexed op, under its own name
+        ("Weighted: send_counts must have world_size entries",
+         (x, 0, [2, 2], [4]), dict(send_weights=w4)),
+        ("Weighted: recv_counts must have world_size entries",
+         (x, 0, [4], [2, 2]), dict(send_weights=w4)),
+        ("Weighted: negative send count -1", (x, 0, [-1], [4]),
+         dict(send_weights=w4)),
+        ("Weighted: negative recv count -2", (x, 0, [4], [-2]),
+         dict(send_weights=w4)),
+        ("Weighted: max_repeat must be >= 1, got 0", (x, 0, [4], [4]),
+         dict(send_weights=w4, max_repeat=0)),
+        ("Weighted: without a send_index the sum of send_counts \\(3\\) must "
+         "equal the axis size \\(4\\)", (x, 0, [3], [3]),
+         dict(send_weights=w4[:3])),
+        ("Weighted: out_size is required with a recv_index", (x, 0, [4], [4]),
+         dict(recv_index=i4, recv_weights=w4)),
+        ("Weighted: out_size must be >= 0, got -1", (x, 0, [4], [4]),
+         dict(send_weights=w4, out_size=-1)),
+        ("Weighted: send_index must be a 1-D tensor of length 4",
+         (x, 0, [4], [4]), dict(send_index=i4[:3], send_weights=w4)),
+        ("Weighted: send_index must be an int64", (x, 0, [4], [4]),
+         dict(send_index=i4.int(), send_weights=w4)),
+        ("Weighted: recv_index must be on the tensor's device",
+         (x, 0, [4], [4]),
+         dict(recv_index=i4.to("meta"), recv_weights=w4, out_size=4)),
+        ("Weighted: recv_index entries must lie in \\[0, 3\\)",
+         (x, 0, [4], [4]),
+         dict(recv_index=i4, recv_weights=w4, out_size=3, max_repeat=2)),
+        ("Weighted: a slice occurs 2 times in send_index, more than "
+         "max_repeat = 1", (x, 0, [4], [4]),
+         dict(send_index=i4, send_weights=w4)),
     ]:
         with pytest.raises(RuntimeError, match=match):
             f(*args, **kw)
