@@ -45,6 +45,8 @@ static auto communicator_class =
         .def("GetSize", &Communicator::GetSize)
         .def("Allreduce", &Communicator::Allreduce)
         .def("AllreduceCompressed", &Communicator::AllreduceCompressed)
+        .def("AllreduceCompressedStochastic",
+             &Communicator::AllreduceCompressedStochastic)
         .def("Bcast_", &Communicator::Bcast_)
         .def("Reduce_", &Communicator::Reduce_)
         .def("Gather", &Communicator::Gather)
@@ -52,6 +54,8 @@ static auto communicator_class =
         .def("Reducescatter", &Communicator::Reducescatter)
         .def("ReducescatterCompressed",
              &Communicator::ReducescatterCompressed)
+        .def("ReducescatterCompressedStochastic",
+             &Communicator::ReducescatterCompressedStochastic)
         .def("AllgatherCompressed", &Communicator::AllgatherCompressed)
         .def("AlltoallCompressed", &Communicator::AlltoallCompressed)
         .def("Scatter", &Communicator::Scatter)
@@ -121,6 +125,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("_pairloc_reduce", &m4a::debug_pairloc_reduce);
   m.def("_mx8_quantize", &m4a::debug_mx8_quantize);
   m.def("_mx8_reduce", &m4a::debug_mx8_reduce);
+  m.def("_mx8_quantize_sr", &m4a::debug_mx8_quantize_sr, py::arg("x"),
+        py::arg("seed"), py::arg("stream"), py::arg("rank"), py::arg("n0"));
+  m.def("_mx8_reduce_sr", &m4a::debug_mx8_reduce_sr, py::arg("payload"),
+        py::arg("scales"), py::arg("seed"), py::arg("stream"),
+        py::arg("rank"), py::arg("n0"));
   m.def("_mx8_dequantize", &m4a::debug_mx8_dequantize, py::arg("payload"),
         py::arg("scales"), py::arg("numel"), py::arg("dtype"),
         py::arg("out") = c10::optional<at::Tensor>());

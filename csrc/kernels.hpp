@@ -106,6 +106,40 @@ void launch_mx8_quantize(const void* in, void* payload, void* scales,
 void launch_mx8_reduce(const void* payload_in, const void* scales_in,
                        void* payload_out, void* scales_out, int64_t n_groups,
                        int nranks, hipStream_t stream);
+// The stochastic-rounding siblings of the two launchers above, for gradient
+// reductions: the same scales, layout and lane layout, but the step to e4m3
+// rounds up with the probability of the discarded fraction (the rule is
+// mx8_quantize_groups_sr in csrc/ops.cpp). Element i of the call is element
+// n0 + i of a logical stream, n0 a multiple of 32, and takes its 16 random
+// bits from a hash of (k0, k1, n0 + i) alone: the bytes do not depend on the
+// grid, on the vector/twin path or on how a stream is cut into calls.
+void launch_mx8_quantize_sr(const void* in, void* payload, void* scales,
+                            int64_t n_elems, int dtype, uint32_t k0,
+                            uint32_t k1, int64_t n0, hipStream_t stream);
+void launch_mx8_reduce_sr(const void* payload_in, const void* scales_in,
+                          void* payload_out, void* scales_out,
+                          int64_t n_groups, int nranks, uint32_t k0,
+                          uint32_t k1, int64_t n0, hipStream_t stream);
+
+// The key of a stochastic-rounding site: splitmix64 steps over the user's
+// seed, the site's stream number and the quantizing rank, so that sites,
+// ranks and consecutive seeds draw unrelated bits. The composite and the
+// launchers' callers share this one function.
+inline uint64_t mx8_sr_mix(uint64_t z) {
+  z += 0x9e3779b97f4a7c15ull;
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+  return z ^ (z >> 31);
+}
+inline void mx8_sr_key(int64_t seed, int64_t stream, int64_t rank,
+                       uint32_t* k0, uint32_t* k1) {
+  uint64_t z = mx8_sr_mix((uint64_t)seed);
+  z = mx8_sr_mix(z ^ (uint64_t)stream);
+  z = mx8_sr_mix(z ^ (uint64_t)rank);
+  *k0 = (uint32_t)z;
+  *k1 = (uint32_t)(z >> 32);
+}
+
 // Dequantize into exactly n_elems elements of the given dtype (RNE).
 void launch_mx8_dequantize(const void* payload, const void* scales, void* out,
                            int64_t n_elems, int dtype, hipStream_t stream);

@@ -54,6 +54,8 @@
 //   dequantize_rowdot : the weights' gradient, one dot product per received
 //                slice over a group of 8 to 64 lanes; the one reduction here.
 // Each of them has a twin for any slice length and alignment.
+// quantize and reduce also exist with stochastic rounding (launch_mx8_*_sr):
+// the same kernels under another rounding policy, see "rounding policies".
 // The first four have a one-thread-per-group scalar twin for base pointers
 // that miss the vector alignment (e.g. a contiguous x[1:] view); the partial
 // last group of their vector kernels goes through the same scalar group
@@ -208,12 +210,92 @@ __device__ inline unsigned amax_bits_of(const float (&x)[N]) {
   return a;
 }
 
-// four values -> one packed payload dword
-__device__ inline unsigned quant4(float a, float b, float c, float d, int E) {
-  return (unsigned)f32_to_e4m3(ldexpf(a, -E)) |
-         ((unsigned)f32_to_e4m3(ldexpf(b, -E)) << 8) |
-         ((unsigned)f32_to_e4m3(ldexpf(c, -E)) << 16) |
-         ((unsigned)f32_to_e4m3(ldexpf(d, -E)) << 24);
+// ---- rounding policies ----------------------------------------------------
+//
+// The step y -> e4m3 byte of the codec, y = x * 2^-E with |y| <= 448. A policy
+// is called as rnd(y, k), k the element's index within the lane (or within
+// the group in the scalar routines). Rne is the codec's own rule and the
+// default everywhere, in the way NoPre is the default Pre.
+struct Rne {
+  __device__ u8 operator()(float y, int) const { return f32_to_e4m3(y); }
+};
+
+// Stochastic rounding (the rule is normative in csrc/ops.cpp,
+// mx8_quantize_groups_sr). The grid around y has ulp = 2^(e-3),
+// e = max(floor(log2|y|), -6); with t = |y|/ulp = fl + frac the rule rounds
+// up iff frac >= (65536 - r) * 2^-16 for the element's 16 random bits r. The
+// threshold is a multiple of 2^-16, so only floor(frac * 2^16) takes part and
+// the comparison is the carry out of the low half of t16 + r,
+// t16 = floor(t * 2^16) < 2^20:  fl + up = (t16 + r) >> 16  in [0, 16].
+// The e4m3 byte of (fl + up) * ulp is then plain integer arithmetic: with the
+// biased exponent em = e + 127 >= 121 it is ((em - 121) << 3) + (fl + up):
+// subnormal or the first normal binade for em == 121 (fl + up <= 8 counts
+// ulps of 2^-9), and for em > 121, where fl >= 8, the exponent field
+// em - 120 over mantissa fl + up - 8, the carry of fl + up == 16 going into
+// the exponent. |y| <= 448 has fl + up <= 14 in the top binade, so 0x7e is
+// the largest byte: the rule cannot saturate. Ten VALU operations per
+// element and no use of the hardware conversion.
+//
+// The random bits are counter-based: element n of the logical stream takes
+// half of the hash word of its aligned pair j = n >> 1,
+//   w = h((h(lo32(j) ^ k0) + hi32(j)) ^ k1),  r = n & 1 ? w >> 16 : w & 0xffff,
+// so a byte depends on (key, n) alone, never on the grid, the lane layout or
+// the vector/twin path. A lane owns 2*W consecutive elements from a multiple
+// of 2*W on (the stream's first index n0 is a multiple of 32), so its W words
+// are j0 + slot*W + 0..W-1 without a carry out of the low word.
+__device__ inline unsigned sr_hash(unsigned x) {
+  x ^= x >> 16;
+  x *= 0x7feb352du;
+  x ^= x >> 15;
+  x *= 0x846ca68bu;
+  x ^= x >> 16;
+  return x;
+}
+
+template <int W>
+struct SrLane {
+  unsigned w[W];
+  __device__ u8 operator()(float y, int k) const {
+    const unsigned u = __float_as_uint(y);
+    const unsigned r = (k & 1) ? w[k >> 1] >> 16 : w[k >> 1] & 0xffffu;
+    unsigned em = (u >> 23) & 0xffu;
+    em = em > 121u ? em : 121u;  // y == 0 and tiny y sit on the 2^-9 grid
+    const unsigned t16 = (unsigned)ldexpf(fabsf(y), 146 - (int)em);
+    return (u8)(((u >> 24) & 0x80u) | (((em - 121u) << 3) + ((t16 + r) >> 16)));
+  }
+};
+
+// By value in the kernel arguments: the key words and the pair index of the
+// stream's first element.
+struct SrKey {
+  unsigned k0, k1;
+  long long j0;
+};
+
+// The policy of lane slot `slot` (of 2*W elements). Without a key it is Rne:
+// the round-to-nearest kernels pass none and stay the code they were. The
+// high word of the pair index is taken once per slot.
+template <int W>
+__device__ inline Rne lane_rounding(long long) { return Rne{}; }
+template <int W>
+__device__ inline SrLane<W> lane_rounding(long long slot, const SrKey& key) {
+  const long long jb = key.j0 + slot * W;
+  const unsigned lo = (unsigned)jb, hi = (unsigned)(jb >> 32);
+  SrLane<W> l;
+  for (int d = 0; d < W; ++d) {
+    l.w[d] = sr_hash((sr_hash((lo + d) ^ key.k0) + hi) ^ key.k1);
+  }
+  return l;
+}
+
+// four values -> one packed payload dword; k: index of `a` within the lane
+template <typename Rnd = Rne>
+__device__ inline unsigned quant4(float a, float b, float c, float d, int E,
+                                  const Rnd& rnd = Rnd{}, int k = 0) {
+  return (unsigned)rnd(ldexpf(a, -E), k) |
+         ((unsigned)rnd(ldexpf(b, -E), k + 1) << 8) |
+         ((unsigned)rnd(ldexpf(c, -E), k + 2) << 16) |
+         ((unsigned)rnd(ldexpf(d, -E), k + 3) << 24);
 }
 
 // Gather the wave's scale bytes (group j's byte lives in lane j*LPG) so
@@ -244,26 +326,28 @@ __device__ inline void store_scales(u8* __restrict__ sc, long long gbase,
 
 // ---- scalar group routines (any alignment, partial groups) --------------
 
+template <typename Rnd = Rne>
 __device__ inline void encode_group_scalar(const float (&x)[32],
                                            u8* __restrict__ pay,
-                                           u8* __restrict__ sc) {
+                                           u8* __restrict__ sc,
+                                           const Rnd& rnd = Rnd{}) {
   int E;
   const int sb = mx8_scale_byte(amax_bits_of(x), &E);
   for (int k = 0; k < 32; ++k) {
-    pay[k] = sb == 255 ? (u8)0 : f32_to_e4m3(ldexpf(x[k], -E));
+    pay[k] = sb == 255 ? (u8)0 : rnd(ldexpf(x[k], -E), k);
   }
   *sc = (u8)sb;
 }
 
-template <int K>
+template <int K, typename Rnd = Rne>
 __device__ inline void quant_group_scalar(
     const typename Elem<K>::type* __restrict__ in, int cnt,
-    u8* __restrict__ pay, u8* __restrict__ sc) {
+    u8* __restrict__ pay, u8* __restrict__ sc, const Rnd& rnd = Rnd{}) {
   float x[32];
   for (int k = 0; k < 32; ++k) {
     x[k] = k < cnt ? elem_to_f32<K>(in[k]) : 0.0f;
   }
-  encode_group_scalar(x, pay, sc);
+  encode_group_scalar(x, pay, sc, rnd);
 }
 
 template <int K>
@@ -320,9 +404,10 @@ __device__ inline void load_chunk(const void* __restrict__ in, long long src,
 // by xor-shuffles, so every lane of the wave must call this; a lane that
 // stores writes its EPL payload bytes at lane slot i of `pay`. Returns the
 // group's scale byte.
-template <int K>
+template <int K, typename Rnd = Rne>
 __device__ inline int quant_lane(const float (&x)[kEPL<K>], bool store,
-                                 u8* __restrict__ pay, long long i) {
+                                 u8* __restrict__ pay, long long i,
+                                 const Rnd& rnd = Rnd{}) {
   constexpr int EPL = kEPL<K>;
   unsigned a = amax_bits_of(x);
   for (int m = 1; m < kLPG<K>; m <<= 1) {
@@ -332,7 +417,8 @@ __device__ inline int quant_lane(const float (&x)[kEPL<K>], bool store,
   int E;
   const int sb = mx8_scale_byte(a, &E);
   if (store) {
-    const unsigned lo = sb == 255 ? 0u : quant4(x[0], x[1], x[2], x[3], E);
+    const unsigned lo =
+        sb == 255 ? 0u : quant4(x[0], x[1], x[2], x[3], E, rnd, 0);
     if constexpr (K == kF32) {
       __builtin_nontemporal_store(lo, reinterpret_cast<unsigned*>(pay) + i);
     } else {
@@ -340,7 +426,8 @@ __device__ inline int quant_lane(const float (&x)[kEPL<K>], bool store,
       o[0] = lo;
       o[1] = sb == 255
                  ? 0u
-                 : quant4(x[EPL - 4], x[EPL - 3], x[EPL - 2], x[EPL - 1], E);
+                 : quant4(x[EPL - 4], x[EPL - 3], x[EPL - 2], x[EPL - 1], E,
+                          rnd, EPL - 4);
       __builtin_nontemporal_store(o, reinterpret_cast<v2u*>(pay) + i);
     }
   }
@@ -396,10 +483,12 @@ __device__ inline bool sum_copies(const u8* __restrict__ pin,
 
 // ---- quantize -----------------------------------------------------------
 
-template <int K>
+// Key is empty (round to nearest) or one SrKey (stochastic rounding, see
+// lane_rounding); the same holds for the twin and the two reduce kernels.
+template <int K, typename... Key>
 __global__ __launch_bounds__(256) void mx8_quantize_kernel(
     const void* __restrict__ in, u8* __restrict__ pay, u8* __restrict__ sc,
-    long long nfull, long long N) {
+    long long nfull, long long N, Key... key) {
   using T = typename Elem<K>::type;
   constexpr int LPG = kLPG<K>;
   const long long total = nfull * LPG;
@@ -413,37 +502,41 @@ __global__ __launch_bounds__(256) void mx8_quantize_kernel(
     const bool act = i < total;
     float x[kEPL<K>];
     load_chunk<K>(in, i, act, x);
-    const int sb = quant_lane<K>(x, act, pay, i);
+    const int sb =
+        quant_lane<K>(x, act, pay, i, lane_rounding<kEPL<K> / 2>(i, key...));
     store_scales<LPG>(sc, i0 / LPG, nfull, sb, lane);
   }
   // zero-padded partial last group
   const int tail = (int)(N - nfull * 32);
   if (tail > 0 && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
     quant_group_scalar<K>(reinterpret_cast<const T*>(in) + nfull * 32, tail,
-                          pay + nfull * 32, sc + nfull);
+                          pay + nfull * 32, sc + nfull,
+                          lane_rounding<16>(nfull, key...));
   }
 }
 
-template <int K>
+template <int K, typename... Key>
 __global__ __launch_bounds__(256) void mx8_quantize_kernel_scalar(
     const void* __restrict__ in, u8* __restrict__ pay, u8* __restrict__ sc,
-    long long G, long long N) {
+    long long G, long long N, Key... key) {
   using T = typename Elem<K>::type;
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < G;
        g += stride) {
     const long long left = N - g * 32;
     quant_group_scalar<K>(reinterpret_cast<const T*>(in) + g * 32,
-                          left < 32 ? (int)left : 32, pay + g * 32, sc + g);
+                          left < 32 ? (int)left : 32, pay + g * 32, sc + g,
+                          lane_rounding<16>(g, key...));
   }
 }
 
 // ---- reduce -------------------------------------------------------------
 
+template <typename... Key>
 __global__ __launch_bounds__(256) void mx8_reduce_kernel(
     const u8* __restrict__ pin, const u8* __restrict__ sin,
     u8* __restrict__ pout, u8* __restrict__ sout, long long n,
-    long long nranks) {
+    long long nranks, Key... key) {
   const long long total = n * 2;  // 16-byte vectors per copy
   const long long stride = (long long)gridDim.x * blockDim.x;
   const int lane = threadIdx.x & 63;
@@ -464,11 +557,12 @@ __global__ __launch_bounds__(256) void mx8_reduce_kernel(
     int E;
     const int sb = mx8_scale_byte(a, &E);
     if (act) {
+      const auto rnd = lane_rounding<8>(i, key...);
       v4u w;
       for (int d = 0; d < 4; ++d) {
         w[d] = sb == 255 ? 0u
                          : quant4(acc[4 * d], acc[4 * d + 1], acc[4 * d + 2],
-                                  acc[4 * d + 3], E);
+                                  acc[4 * d + 3], E, rnd, 4 * d);
       }
       __builtin_nontemporal_store(w, reinterpret_cast<v4u*>(pout) + i);
     }
@@ -476,10 +570,11 @@ __global__ __launch_bounds__(256) void mx8_reduce_kernel(
   }
 }
 
+template <typename... Key>
 __global__ __launch_bounds__(256) void mx8_reduce_kernel_scalar(
     const u8* __restrict__ pin, const u8* __restrict__ sin,
     u8* __restrict__ pout, u8* __restrict__ sout, long long n,
-    long long nranks) {
+    long long nranks, Key... key) {
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < n;
        g += stride) {
@@ -501,7 +596,8 @@ __global__ __launch_bounds__(256) void mx8_reduce_kernel_scalar(
       }
     }
     if (bad) acc[0] = __uint_as_float(kQNaNBits);
-    encode_group_scalar(acc, pout + g * 32, sout + g);
+    encode_group_scalar(acc, pout + g * 32, sout + g,
+                        lane_rounding<16>(g, key...));
   }
 }
 
@@ -1493,21 +1589,50 @@ void by_width_mode(long long work, bool indexed, int64_t rows, F&& f) {
   });
 }
 
-template <int K>
+// key: nothing, or the SrKey of the stochastic kernels
+template <int K, typename... Key>
 void launch_quantize_t(const void* in, void* pay, void* sc, int64_t N,
-                       hipStream_t stream) {
+                       hipStream_t stream, Key... key) {
   constexpr int LPG = kLPG<K>;
   const long long G = (N + 31) / 32;
   const long long nfull = N / 32;
   if (aligned(in, 16) && aligned(pay, 32 / LPG)) {
-    hipLaunchKernelGGL((mx8_quantize_kernel<K>), dim3(grid_for(nfull * LPG)),
-                       dim3(256), 0, stream, in, static_cast<u8*>(pay),
-                       static_cast<u8*>(sc), nfull, (long long)N);
+    hipLaunchKernelGGL((mx8_quantize_kernel<K, Key...>),
+                       dim3(grid_for(nfull * LPG)), dim3(256), 0, stream, in,
+                       static_cast<u8*>(pay), static_cast<u8*>(sc), nfull,
+                       (long long)N, key...);
   } else {
-    hipLaunchKernelGGL((mx8_quantize_kernel_scalar<K>), dim3(grid_for(G)),
-                       dim3(256), 0, stream, in, static_cast<u8*>(pay),
-                       static_cast<u8*>(sc), G, (long long)N);
+    hipLaunchKernelGGL((mx8_quantize_kernel_scalar<K, Key...>),
+                       dim3(grid_for(G)), dim3(256), 0, stream, in,
+                       static_cast<u8*>(pay), static_cast<u8*>(sc), G,
+                       (long long)N, key...);
   }
+}
+
+template <typename... Key>
+void launch_reduce_t(const void* payload_in, const void* scales_in,
+                     void* payload_out, void* scales_out, int64_t n_groups,
+                     int nranks, hipStream_t stream, Key... key) {
+  const u8* pin = static_cast<const u8*>(payload_in);
+  const u8* sin = static_cast<const u8*>(scales_in);
+  u8* pout = static_cast<u8*>(payload_out);
+  u8* sout = static_cast<u8*>(scales_out);
+  if (aligned(pin, 16) && aligned(pout, 16)) {
+    hipLaunchKernelGGL((mx8_reduce_kernel<Key...>),
+                       dim3(grid_for(n_groups * 2)), dim3(256), 0, stream, pin,
+                       sin, pout, sout, (long long)n_groups,
+                       (long long)nranks, key...);
+  } else {
+    hipLaunchKernelGGL((mx8_reduce_kernel_scalar<Key...>),
+                       dim3(grid_for(n_groups)), dim3(256), 0, stream, pin,
+                       sin, pout, sout, (long long)n_groups,
+                       (long long)nranks, key...);
+  }
+}
+
+// n0: stream index of the first element, a multiple of 32
+inline SrKey sr_key(uint32_t k0, uint32_t k1, int64_t n0) {
+  return SrKey{k0, k1, (long long)(n0 >> 1)};
 }
 
 template <int K>
@@ -2003,23 +2128,31 @@ void launch_mx8_quantize(const void* in, void* payload, void* scales,
   });
 }
 
+void launch_mx8_quantize_sr(const void* in, void* payload, void* scales,
+                            int64_t n_elems, int dtype, uint32_t k0,
+                            uint32_t k1, int64_t n0, hipStream_t stream) {
+  if (n_elems <= 0) return;
+  by_dtype(dtype, [&](auto k) {
+    launch_quantize_t<k>(in, payload, scales, n_elems, stream,
+                         sr_key(k0, k1, n0));
+  });
+}
+
 void launch_mx8_reduce(const void* payload_in, const void* scales_in,
                        void* payload_out, void* scales_out, int64_t n_groups,
                        int nranks, hipStream_t stream) {
   if (n_groups <= 0) return;
-  const u8* pin = static_cast<const u8*>(payload_in);
-  const u8* sin = static_cast<const u8*>(scales_in);
-  u8* pout = static_cast<u8*>(payload_out);
-  u8* sout = static_cast<u8*>(scales_out);
-  if (aligned(pin, 16) && aligned(pout, 16)) {
-    hipLaunchKernelGGL(mx8_reduce_kernel, dim3(grid_for(n_groups * 2)),
-                       dim3(256), 0, stream, pin, sin, pout, sout,
-                       (long long)n_groups, (long long)nranks);
-  } else {
-    hipLaunchKernelGGL(mx8_reduce_kernel_scalar, dim3(grid_for(n_groups)),
-                       dim3(256), 0, stream, pin, sin, pout, sout,
-                       (long long)n_groups, (long long)nranks);
-  }
+  launch_reduce_t(payload_in, scales_in, payload_out, scales_out, n_groups,
+                  nranks, stream);
+}
+
+void launch_mx8_reduce_sr(const void* payload_in, const void* scales_in,
+                          void* payload_out, void* scales_out,
+                          int64_t n_groups, int nranks, uint32_t k0,
+                          uint32_t k1, int64_t n0, hipStream_t stream) {
+  if (n_groups <= 0) return;
+  launch_reduce_t(payload_in, scales_in, payload_out, scales_out, n_groups,
+                  nranks, stream, sr_key(k0, k1, n0));
 }
 
 void launch_mx8_dequantize(const void* payload, const void* scales, void* out,

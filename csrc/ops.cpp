@@ -872,6 +872,87 @@ std::pair<Tensor, Tensor> mx8_quantize_groups(const Tensor& xg) {
   return {pay.contiguous(), sc.contiguous()};
 }
 
+// Stochastic rounding (normative, like the rule above; the _sr kernels match
+// it byte for byte). Scale byte, shared exponent E, the 255 group and
+// y = x * 2^-E are those of mx8_quantize_groups; only the step y -> e4m3
+// differs:
+//   grid   : e = max(floor(log2|y|), -6) from the exponent field (y == 0 and
+//            fp32-subnormal y take -6), ulp = 2^(e-3), t = |y| / ulp (exact,
+//            in [0, 16), <= 14 in the top binade);
+//   step   : fl = floor(t), frac = t - fl (exact); with the element's 16
+//            random bits r, round up iff frac >= (65536 - r) * 2^-16, so the
+//            probability of rounding up is frac to within 2^-16 and
+//            frac == 0 never does; q = copysign((fl + up) * ulp, y) is an
+//            e4m3 value with |q| <= 448 and the payload byte is its exact
+//            conversion. Signed zeros keep their sign.
+//   bits   : counter-based, a function of the key (k0, k1) and the int64
+//            index n of the element in its logical stream alone. With
+//            h(x): x ^= x>>16; x *= 0x7feb352d; x ^= x>>15; x *= 0x846ca68b;
+//            x ^= x>>16 (uint32) and j = n >> 1:
+//              w = h((h(lo32(j) ^ k0) + hi32(j)) ^ k1),
+//              r = n & 1 ? w >> 16 : w & 0xffff.
+//   key    : mx8_sr_key(seed, stream, rank) of csrc/kernels.hpp.
+struct Mx8SrKey {
+  uint32_t k0, k1;
+  int64_t n0;  // stream index of the first element, a multiple of 32
+};
+
+Mx8SrKey mx8_sr_site(int64_t seed, int64_t stream, int64_t rank, int64_t n0) {
+  TORCH_CHECK(n0 >= 0 && n0 % 32 == 0,
+              "mpi4torch_amd: a stochastic-rounding stream starts at a "
+              "multiple of 32, got ", n0);
+  Mx8SrKey key{0, 0, n0};
+  mx8_sr_key(seed, stream, rank, &key.k0, &key.k1);
+  return key;
+}
+
+// The 16 random bits of elements n0 .. n0+count-1 as int64. uint32 arithmetic
+// is done in int64 and masked: a wrapped int64 product keeps its low 32 bits.
+Tensor mx8_sr_bits(const Mx8SrKey& key, int64_t count,
+                   const at::TensorOptions& opts) {
+  const int64_t M = 0xffffffffll;
+  auto h = [&](Tensor x) {
+    x = x.bitwise_xor(x.bitwise_right_shift(16));
+    x = (x * (int64_t)0x7feb352dll).bitwise_and(M);
+    x = x.bitwise_xor(x.bitwise_right_shift(15));
+    x = (x * (int64_t)0x846ca68bll).bitwise_and(M);
+    return x.bitwise_xor(x.bitwise_right_shift(16));
+  };
+  auto n = at::arange(count, opts.dtype(at::kLong)) + key.n0;
+  auto j = n.bitwise_right_shift(1);
+  auto lo = j.bitwise_and(M);
+  auto hi = j.bitwise_right_shift(32);
+  auto w = h((h(lo.bitwise_xor((int64_t)key.k0)) + hi)
+                 .bitwise_and(M)
+                 .bitwise_xor((int64_t)key.k1));
+  return at::where(n.bitwise_and(1).ne(0), w.bitwise_right_shift(16),
+                   w.bitwise_and(0xffff));
+}
+
+// xg: [G, 32] fp32 -> (payload [G, 32] u8, scales [G] u8); group g's element
+// k is element key.n0 + 32*g + k of the stream.
+std::pair<Tensor, Tensor> mx8_quantize_groups_sr(const Tensor& xg,
+                                                 const Mx8SrKey& key) {
+  auto rne = mx8_quantize_groups(xg);  // the scale bytes are the rule's own
+  auto finite = rne.second.ne(255);
+  auto E = (rne.second.to(at::kInt) - 127).clamp(-127, 127);
+  auto y = xg.masked_fill(finite.logical_not().unsqueeze(1), 0) *
+           mx8_pow2(-E).unsqueeze(1);
+  auto ay = y.abs();
+  auto e = (ay.contiguous().view(at::kInt).bitwise_right_shift(23) - 127)
+               .clamp_min(-6);
+  auto t = ay * mx8_pow2(3 - e);
+  auto fl = t.floor();
+  auto frac = t - fl;
+  auto r = mx8_sr_bits(key, xg.numel(), xg.options()).view(xg.sizes());
+  auto thr = (65536 - r).to(at::kFloat) * (1.0f / 65536.0f);
+  auto up = frac.ge(thr).to(at::kFloat);
+  auto q = at::copysign((fl + up) * mx8_pow2(e - 3), y);
+  auto pay = q.to(at::kFloat8_e4m3fn).view(at::kByte);
+  pay = at::where(finite.unsqueeze(1), pay, at::zeros_like(pay));
+  return {pay.contiguous(), rne.second};
+}
+
 // payload [G, 32] u8, scales [G] u8 -> [G, 32] fp32
 Tensor mx8_dequantize_groups(const Tensor& pay, const Tensor& sc) {
   auto v = pay.contiguous().view(at::kFloat8_e4m3fn).to(at::kFloat);
@@ -902,10 +983,13 @@ Tensor out_or_empty(const c10::optional<Tensor>& out, at::IntArrayRef sizes,
   return out.has_value() ? *out : at::empty(sizes, opts);
 }
 
-// flat contiguous x -> (payload [G*32] u8, scales [G] u8), G = ceil(N/32)
+// flat contiguous x -> (payload [G*32] u8, scales [G] u8), G = ceil(N/32).
+// With `sr` the rounding is stochastic under that key, x[0] being element
+// sr->n0 of the stream.
 std::pair<Tensor, Tensor> mx8_quantize(
     const Tensor& x, const c10::optional<Tensor>& payload_out = c10::nullopt,
-    const c10::optional<Tensor>& scales_out = c10::nullopt) {
+    const c10::optional<Tensor>& scales_out = c10::nullopt,
+    const Mx8SrKey* sr = nullptr) {
   const int dt = mx8_dtype_code(x.scalar_type());
   const int64_t N = x.numel();
   const int64_t G = (N + 31) / 32;
@@ -913,13 +997,20 @@ std::pair<Tensor, Tensor> mx8_quantize(
   auto pay = out_or_empty(payload_out, {G * 32}, bopts);
   auto sc = out_or_empty(scales_out, {G}, bopts);
   if (x.is_cuda()) {
-    launch_mx8_quantize(x.data_ptr(), pay.data_ptr(), sc.data_ptr(), N, dt,
-                        current_gpu_stream(x));
+    if (sr) {
+      launch_mx8_quantize_sr(x.data_ptr(), pay.data_ptr(), sc.data_ptr(), N,
+                             dt, sr->k0, sr->k1, sr->n0,
+                             current_gpu_stream(x));
+    } else {
+      launch_mx8_quantize(x.data_ptr(), pay.data_ptr(), sc.data_ptr(), N, dt,
+                          current_gpu_stream(x));
+    }
     return {pay, sc};
   }
   auto padded = at::zeros({G * 32}, x.options().dtype(at::kFloat));
   padded.narrow(0, 0, N).copy_(x.view({-1}));
-  auto ps = mx8_quantize_groups(padded.view({G, 32}));
+  auto ps = sr ? mx8_quantize_groups_sr(padded.view({G, 32}), *sr)
+               : mx8_quantize_groups(padded.view({G, 32}));
   if (!payload_out.has_value()) return {ps.first.view({-1}), ps.second};
   pay.copy_(ps.first.view({-1}));
   sc.copy_(ps.second);
@@ -938,16 +1029,25 @@ Tensor mx8_sum_copies(const Tensor& pin, const Tensor& sin, int64_t n, int P) {
   return acc;
 }
 
-// P copies: pin [P * n*32], sin [P * n] -> pout [n*32], sout [n] (views ok)
+// P copies: pin [P * n*32], sin [P * n] -> pout [n*32], sout [n] (views ok).
+// With `sr` the requantization rounds stochastically under that key, group 0
+// starting at element sr->n0 of the stream.
 void mx8_reduce(const Tensor& pin, const Tensor& sin, Tensor& pout,
-                Tensor& sout, int64_t n, int P) {
+                Tensor& sout, int64_t n, int P, const Mx8SrKey* sr = nullptr) {
   if (n == 0) return;
   if (pin.is_cuda()) {
-    launch_mx8_reduce(pin.data_ptr(), sin.data_ptr(), pout.data_ptr(),
-                      sout.data_ptr(), n, P, current_gpu_stream(pin));
+    if (sr) {
+      launch_mx8_reduce_sr(pin.data_ptr(), sin.data_ptr(), pout.data_ptr(),
+                           sout.data_ptr(), n, P, sr->k0, sr->k1, sr->n0,
+                           current_gpu_stream(pin));
+    } else {
+      launch_mx8_reduce(pin.data_ptr(), sin.data_ptr(), pout.data_ptr(),
+                        sout.data_ptr(), n, P, current_gpu_stream(pin));
+    }
     return;
   }
-  auto ps = mx8_quantize_groups(mx8_sum_copies(pin, sin, n, P));
+  auto sum = mx8_sum_copies(pin, sin, n, P);
+  auto ps = sr ? mx8_quantize_groups_sr(sum, *sr) : mx8_quantize_groups(sum);
   pout.copy_(ps.first.view({-1}));
   sout.copy_(ps.second);
 }
@@ -1037,14 +1137,21 @@ std::pair<Tensor, Tensor> mx8_exchange_blocks(Transport& tr, const Tensor& pay,
 // quantized exactly once; nothing goes back on the wire. Staging is two
 // buffers of ~33/32 * P*L bytes; the wire carries (P-1)*33*ceil(L/32) bytes
 // per rank.
-Tensor mx8_reducescatter(Transport& tr, const Tensor& packed, int64_t L) {
+// With `seed` the quantization rounds stochastically: stream 0 under this
+// rank, an element's index being its place in the quantized stream (block p
+// starts at p*Gb*32).
+Tensor mx8_reducescatter(Transport& tr, const Tensor& packed, int64_t L,
+                         const int64_t* seed = nullptr) {
   const int P = tr.size();
   const int64_t Gb = (L + 31) / 32;
   auto bopts = packed.options().dtype(at::kByte);
+  Mx8SrKey key{};
+  if (seed) key = mx8_sr_site(*seed, 0, tr.rank(), 0);
   Tensor pay, sc;
   if (L % 32 == 0) {
     // block-relative groups coincide with flat groups: one launch
-    auto q = mx8_quantize(packed);
+    auto q = mx8_quantize(packed, c10::nullopt, c10::nullopt,
+                          seed ? &key : nullptr);
     pay = q.first;
     sc = q.second;
   } else {
@@ -1052,9 +1159,10 @@ Tensor mx8_reducescatter(Transport& tr, const Tensor& packed, int64_t L) {
     pay = at::empty({(int64_t)P * Gb * 32}, bopts);
     sc = at::empty({(int64_t)P * Gb}, bopts);
     for (int p = 0; p < P; ++p) {
+      key.n0 = (int64_t)p * Gb * 32;
       mx8_quantize(packed.narrow(0, (int64_t)p * L, L),
                    pay.narrow(0, (int64_t)p * Gb * 32, Gb * 32),
-                   sc.narrow(0, (int64_t)p * Gb, Gb));
+                   sc.narrow(0, (int64_t)p * Gb, Gb), seed ? &key : nullptr);
     }
   }
   auto stg = mx8_exchange_blocks(tr, pay, sc, Gb);
@@ -1574,7 +1682,12 @@ Tensor mx8_alltoall_pairwise(
 // rank decodes the same bytes, so results are identical across ranks.
 // Staging is ~33/32 * numel bytes twice (quantized input, P copies of the
 // owned block), never P * numel.
-Tensor mx8_allreduce(Transport& tr, const Tensor& in) {
+// With `seed` both quantizations round stochastically: the input under
+// stream `stream0` and this rank, the owned block under stream0 + 1 and rank
+// 0 with an element's index in the whole tensor, so the reduced bytes do not
+// depend on how the groups are split over the ranks.
+Tensor mx8_allreduce(Transport& tr, const Tensor& in,
+                     const int64_t* seed = nullptr, int64_t stream0 = 0) {
   const int P = tr.size();
   const int me = tr.rank();
   const int64_t N = in.numel();
@@ -1585,7 +1698,13 @@ Tensor mx8_allreduce(Transport& tr, const Tensor& in) {
   auto nz_narrow = [](const Tensor& t, int64_t off, int64_t len) {
     return len > 0 ? t.narrow(0, off, len) : t.narrow(0, 0, 0);
   };
-  auto q = mx8_quantize(in.view({-1}));
+  Mx8SrKey qkey{}, rkey{};
+  if (seed) {
+    qkey = mx8_sr_site(*seed, stream0, me, 0);
+    rkey = mx8_sr_site(*seed, stream0 + 1, 0, displs[me] * 32);
+  }
+  auto q = mx8_quantize(in.view({-1}), c10::nullopt, c10::nullopt,
+                        seed ? &qkey : nullptr);
   const int64_t cm = counts[me];
   // phase 1: one grouped exchange carrying payload and scales
   auto bopts = in.options().dtype(at::kByte);
@@ -1600,7 +1719,7 @@ Tensor mx8_allreduce(Transport& tr, const Tensor& in) {
   auto out_sc = at::empty({G}, bopts);
   auto my_pay = nz_narrow(out_pay, displs[me] * 32, cm * 32);
   auto my_sc = nz_narrow(out_sc, displs[me], cm);
-  mx8_reduce(stg_pay, stg_sc, my_pay, my_sc, cm, P);
+  mx8_reduce(stg_pay, stg_sc, my_pay, my_sc, cm, P, seed ? &rkey : nullptr);
   // phase 3: allgather payload + scales (equal counts on GPU: RCCL, in
   // place; otherwise grouped p2p — same split as hierarchical_allreduce)
   if (G % P == 0 && tr.is_gpu()) {
@@ -1779,6 +1898,49 @@ struct AllreduceCompressedBackward : public M4ANode {
     return out;
   }
 };
+
+Tensor allreduce_compressed_sr(Communicator& comm, const Tensor& input,
+                               int64_t op, int64_t seed, int64_t stream0);
+
+// The same op on the gradient under the other pair of streams (0, 1 forward;
+// 2, 3 backward), so forward and backward never share random bits.
+struct AllreduceCompressedStochasticBackward : public M4ANode {
+  AllreduceCompressedStochasticBackward(int64_t seed, int64_t stream0)
+      : seed(seed), stream0(stream0) {}
+  std::string name() const override {
+    return "M4AAllreduceCompressedStochasticBackward";
+  }
+  variable_list apply(variable_list&& grads) override {
+    variable_list out(1);
+    if (should_compute_output(0)) {
+      out[0] = allreduce_compressed_sr(*comm, grads[0], kSum, seed,
+                                       stream0 ^ 2);
+    }
+    return out;
+  }
+  int64_t seed, stream0;
+};
+
+Tensor allreduce_compressed_sr(Communicator& comm, const Tensor& input,
+                               int64_t op, int64_t seed, int64_t stream0) {
+  const char* who = "AllreduceCompressedStochastic";
+  TORCH_CHECK(op == kSum, "mpi4torch_amd: ", who, " supports MPI_SUM only "
+              "(got ", red_op_name(op), ")");
+  check_mx8_input(who, input);
+  return collective_frame(
+      comm, input,
+      [&](auto c) {
+        return make_node<AllreduceCompressedStochasticBackward>(c, seed,
+                                                                stream0);
+      },
+      [&](Transport& tr, const Tensor& in, const DeviceStager&) {
+        debug_check_collective(comm.group_name(), who, in,
+                               {op, seed, stream0});
+        if (in.numel() == 0) return in.clone();
+        if (world1_shortcut(tr, in)) return fast_clone(in);
+        return mx8_allreduce(tr, in, &seed, stream0);
+      });
+}
 } // namespace
 
 Tensor Communicator::AllreduceCompressed(const Tensor& input, int64_t op) {
@@ -1796,6 +1958,11 @@ Tensor Communicator::AllreduceCompressed(const Tensor& input, int64_t op) {
         if (world1_shortcut(tr, in)) return fast_clone(in);
         return mx8_allreduce(tr, in);
       });
+}
+
+Tensor Communicator::AllreduceCompressedStochastic(const Tensor& input,
+                                                   int64_t op, int64_t seed) {
+  return allreduce_compressed_sr(*this, input, op, seed, 0);
 }
 
 // ---------------------------------------------------------------------------
@@ -2482,9 +2649,13 @@ struct ReducescatterCompressedBackward : public M4ANode {
 };
 } // namespace
 
-Tensor Communicator::ReducescatterCompressed(const Tensor& input,
-                                             int64_t axis) {
-  check_mx8_input("ReducescatterCompressed", input);
+namespace {
+// Both front-ends; `seed` selects stochastic rounding of the quantization.
+Tensor reducescatter_compressed(Communicator& comm, const Tensor& input,
+                                int64_t axis, const int64_t* seed) {
+  const char* who =
+      seed ? "ReducescatterCompressedStochastic" : "ReducescatterCompressed";
+  check_mx8_input(who, input);
   axis = at::maybe_wrap_dim(axis, input.dim());
   auto make_grad_fn = [&](auto comm) {
     return make_node<ReducescatterCompressedBackward>(comm, axis);
@@ -2493,11 +2664,15 @@ Tensor Communicator::ReducescatterCompressed(const Tensor& input,
                   const DeviceStager&) -> Tensor {
     const int P = tr.size();
     TORCH_CHECK(in.size(axis) % P == 0,
-                "mpi4torch_amd: ReducescatterCompressed requires equal "
+                "mpi4torch_amd: ", who, " requires equal "
                 "counts: the axis size (", in.size(axis), ") must be a "
                 "multiple of the world size (", P, "); Reducescatter "
                 "handles variable counts");
-    debug_check_collective(group_name_, "ReducescatterCompressed", in, {axis});
+    if (seed) {
+      debug_check_collective(comm.group_name(), who, in, {axis, *seed});
+    } else {
+      debug_check_collective(comm.group_name(), who, in, {axis});
+    }
     auto outsizes = in.sizes().vec();
     outsizes[axis] = in.size(axis) / P;
     if (in.numel() == 0) return at::empty(outsizes, in.options());
@@ -2518,9 +2693,21 @@ Tensor Communicator::ReducescatterCompressed(const Tensor& input,
       }
       move_axis_blocks(in, axis, displs, counts, blocks, /*pack=*/true);
     }
-    return mx8_reducescatter(tr, packed, L).view(outsizes);
+    return mx8_reducescatter(tr, packed, L, seed).view(outsizes);
   };
-  return collective_frame(*this, input, make_grad_fn, body);
+  return collective_frame(comm, input, make_grad_fn, body);
+}
+} // namespace
+
+Tensor Communicator::ReducescatterCompressed(const Tensor& input,
+                                             int64_t axis) {
+  return reducescatter_compressed(*this, input, axis, nullptr);
+}
+
+Tensor Communicator::ReducescatterCompressedStochastic(const Tensor& input,
+                                                       int64_t axis,
+                                                       int64_t seed) {
+  return reducescatter_compressed(*this, input, axis, &seed);
 }
 
 // ---------------------------------------------------------------------------
@@ -4021,8 +4208,38 @@ std::tuple<Tensor, Tensor> debug_mx8_quantize(const Tensor& x) {
   return std::make_tuple(ps.first, ps.second);
 }
 
+std::tuple<Tensor, Tensor> debug_mx8_quantize_sr(const Tensor& x, int64_t seed,
+                                                 int64_t stream, int64_t rank,
+                                                 int64_t n0) {
+  const auto key = mx8_sr_site(seed, stream, rank, n0);
+  auto ps = mx8_quantize(x.contiguous().view({-1}), c10::nullopt, c10::nullopt,
+                         &key);
+  return std::make_tuple(ps.first, ps.second);
+}
+
+namespace {
+std::tuple<Tensor, Tensor> debug_reduce(const Tensor& payload,
+                                        const Tensor& scales,
+                                        const Mx8SrKey* sr);
+}
+
 std::tuple<Tensor, Tensor> debug_mx8_reduce(const Tensor& payload,
                                             const Tensor& scales) {
+  return debug_reduce(payload, scales, nullptr);
+}
+
+std::tuple<Tensor, Tensor> debug_mx8_reduce_sr(const Tensor& payload,
+                                               const Tensor& scales,
+                                               int64_t seed, int64_t stream,
+                                               int64_t rank, int64_t n0) {
+  const auto key = mx8_sr_site(seed, stream, rank, n0);
+  return debug_reduce(payload, scales, &key);
+}
+
+namespace {
+std::tuple<Tensor, Tensor> debug_reduce(const Tensor& payload,
+                                        const Tensor& scales,
+                                        const Mx8SrKey* sr) {
   TORCH_CHECK(payload.dim() == 2 && scales.dim() == 2 &&
                   payload.scalar_type() == at::kByte &&
                   scales.scalar_type() == at::kByte &&
@@ -4036,9 +4253,10 @@ std::tuple<Tensor, Tensor> debug_mx8_reduce(const Tensor& payload,
   TORCH_CHECK(P >= 1);
   auto pout = at::empty({n * 32}, pin.options());
   auto sout = at::empty({n}, sin.options());
-  mx8_reduce(pin.view({-1}), sin.view({-1}), pout, sout, n, (int)P);
+  mx8_reduce(pin.view({-1}), sin.view({-1}), pout, sout, n, (int)P, sr);
   return std::make_tuple(pout, sout);
 }
+} // namespace
 
 Tensor debug_mx8_dequantize(const Tensor& payload, const Tensor& scales,
                             int64_t numel, at::ScalarType dtype,

@@ -37,6 +37,14 @@ struct Communicator : torch::CustomClassHolder {
   // AllreduceCompressed of the gradient (self-adjoint sum, straight-through
   // quantization). A world of one returns an exact clone.
   at::Tensor AllreduceCompressed(const at::Tensor& input, int64_t op);
+  // AllreduceCompressed with stochastic rounding in both quantizations
+  // (unbiased, for gradients): the random bits are a function of `seed`, the
+  // quantization site, the quantizing rank and the element's index alone, so
+  // equal seeds give identical bytes on all ranks, whatever the launch and
+  // however the groups are split over the ranks. All ranks pass the same
+  // seed. Backward: the same op on the gradient under streams of its own.
+  at::Tensor AllreduceCompressedStochastic(const at::Tensor& input, int64_t op,
+                                           int64_t seed);
   at::Tensor Bcast_(const at::Tensor& input, int64_t root);
   at::Tensor Reduce_(const at::Tensor& input, int64_t op, int64_t root);
   at::Tensor Gather(const at::Tensor& input, int64_t gatheraxis, int64_t root);
@@ -57,6 +65,11 @@ struct Communicator : torch::CustomClassHolder {
   // must be a multiple of the world size. Backward: uncompressed Allgather
   // of the gradient. A world of one returns an exact clone.
   at::Tensor ReducescatterCompressed(const at::Tensor& input, int64_t axis);
+  // ReducescatterCompressed with stochastic rounding in its one
+  // quantization; `seed` as for AllreduceCompressedStochastic. Backward:
+  // uncompressed Allgather.
+  at::Tensor ReducescatterCompressedStochastic(const at::Tensor& input,
+                                               int64_t axis, int64_t seed);
   // Allgather over the mxfp8 wire (MI355X extension): every rank's tensor
   // (equal sizes on `axis`) is quantized once in groups of 32 that start at
   // its first element, payload and scales are allgathered as bytes, and the
@@ -232,6 +245,15 @@ std::tuple<at::Tensor, at::Tensor> debug_mx8_quantize(const at::Tensor& x);
 // payload [P, G*32], scales [P, G] -> (payload [G*32], scales [G])
 std::tuple<at::Tensor, at::Tensor> debug_mx8_reduce(const at::Tensor& payload,
                                                     const at::Tensor& scales);
+// The stochastic-rounding forms of the two above: the key is
+// mx8_sr_key(seed, stream, rank) and the first element is element n0 (a
+// multiple of 32) of the stream.
+std::tuple<at::Tensor, at::Tensor> debug_mx8_quantize_sr(
+    const at::Tensor& x, int64_t seed, int64_t stream, int64_t rank,
+    int64_t n0);
+std::tuple<at::Tensor, at::Tensor> debug_mx8_reduce_sr(
+    const at::Tensor& payload, const at::Tensor& scales, int64_t seed,
+    int64_t stream, int64_t rank, int64_t n0);
 at::Tensor debug_mx8_dequantize(const at::Tensor& payload,
                                 const at::Tensor& scales, int64_t numel,
                                 at::ScalarType dtype,

@@ -151,8 +151,8 @@ class MPI_Communicator:
         """
         return self._comm.Allreduce(tensor, op)
 
-    def AllreduceCompressed(self, tensor: torch.Tensor,
-                            op: int = 2) -> torch.Tensor:
+    def AllreduceCompressed(self, tensor: torch.Tensor, op: int = 2,
+                            seed: Optional[int] = None) -> torch.Tensor:
         """Sum-Allreduce that travels as block-scaled fp8 (MI355X extension).
 
         The tensor (float32, bfloat16 or float16) is quantized to mxfp8 —
@@ -169,10 +169,23 @@ class MPI_Communicator:
         A world of one returns an exact clone: nothing crosses a wire, so
         nothing is compressed.
 
-        Backward: AllreduceCompressed of the gradient. The op is treated as
-        the self-adjoint sum; quantization is straight-through.
+        ``seed`` (an int, the same on all ranks) switches both quantizations
+        from round-to-nearest to stochastic rounding, the choice for
+        gradients: every quantization is then unbiased, so the error
+        averages out over ranks and steps instead of flushing the same small
+        components on every one of them. The random bits are a function of
+        the seed, the quantization site, the quantizing rank and the
+        element's index alone, so the result stays bit-identical on every
+        rank and reproducible; pass a different seed for every call.
+        ``seed=None`` is round-to-nearest.
+
+        Backward: AllreduceCompressed of the gradient (with the seed, under
+        random bits of its own). The op is treated as the self-adjoint sum;
+        quantization is straight-through.
         """
-        return self._comm.AllreduceCompressed(tensor, op)
+        if seed is None:
+            return self._comm.AllreduceCompressed(tensor, op)
+        return self._comm.AllreduceCompressedStochastic(tensor, op, seed)
 
     def Bcast_(self, tensor: torch.Tensor, root: int) -> torch.Tensor:
         """Broadcast from ``root`` (in place). Backward: Reduce_ to root."""
@@ -210,8 +223,8 @@ class MPI_Communicator:
         primitive."""
         return self._comm.Reducescatter(tensor, axis, numelem)
 
-    def ReducescatterCompressed(self, tensor: torch.Tensor,
-                                axis: int = 0) -> torch.Tensor:
+    def ReducescatterCompressed(self, tensor: torch.Tensor, axis: int = 0,
+                                seed: Optional[int] = None) -> torch.Tensor:
         """Sum reduce-scatter that travels as block-scaled fp8 (MI355X
         extension): the ZeRO-2 gradient primitive over the mxfp8 wire.
 
@@ -233,8 +246,13 @@ class MPI_Communicator:
         Backward: Allgather of the gradient along ``axis`` — the exact
         adjoint of the sum; quantization is straight-through and the
         gradient travels uncompressed.
+
+        ``seed`` (an int, the same on all ranks) selects stochastic rounding
+        of the one quantization, as for AllreduceCompressed.
         """
-        return self._comm.ReducescatterCompressed(tensor, axis)
+        if seed is None:
+            return self._comm.ReducescatterCompressed(tensor, axis)
+        return self._comm.ReducescatterCompressedStochastic(tensor, axis, seed)
 
     def AllgatherCompressed(self, tensor: torch.Tensor,
                             axis: int = 0) -> torch.Tensor:

@@ -20,10 +20,11 @@ def allreduce(tensor: torch.Tensor, op: Optional[int] = None, comm=None):
 
 
 def allreduce_compressed(tensor: torch.Tensor, op: Optional[int] = None,
-                         comm=None):
-    """Sum-Allreduce over an mxfp8 wire (33/32 byte per element)."""
+                         comm=None, seed: Optional[int] = None):
+    """Sum-Allreduce over an mxfp8 wire (33/32 byte per element); an int
+    ``seed`` selects stochastic rounding."""
     return _comm(comm).AllreduceCompressed(
-        tensor, _m.MPI_SUM if op is None else op)
+        tensor, _m.MPI_SUM if op is None else op, seed)
 
 
 def bcast_(tensor: torch.Tensor, root: int = 0, comm=None):
@@ -58,9 +59,11 @@ def reducescatter(tensor: torch.Tensor, axis: int = 0, numelem: int = 1,
     return _comm(comm).Reducescatter(tensor, axis, numelem)
 
 
-def reducescatter_compressed(tensor: torch.Tensor, axis: int = 0, comm=None):
-    """Sum reduce-scatter over an mxfp8 wire (equal blocks along ``axis``)."""
-    return _comm(comm).ReducescatterCompressed(tensor, axis)
+def reducescatter_compressed(tensor: torch.Tensor, axis: int = 0, comm=None,
+                             seed: Optional[int] = None):
+    """Sum reduce-scatter over an mxfp8 wire (equal blocks along ``axis``);
+    an int ``seed`` selects stochastic rounding."""
+    return _comm(comm).ReducescatterCompressed(tensor, axis, seed)
 
 
 def allgather_compressed(tensor: torch.Tensor, axis: int = 0, comm=None):

@@ -25,7 +25,12 @@ with the blocking AllreduceCompressed (block-scaled fp8 wire, 33/32 byte
 per element instead of 2 or 4). Buckets are then not launched eagerly —
 there is no non-blocking compressed allreduce yet — but flattened and
 reduced in bucket order by finish_gradient_sync; averaging happens after
-the reduction, as for uncompressed buckets.
+the reduction, as for uncompressed buckets. ``grad_compression="mxfp8-sr"``
+is the same wire with stochastic rounding (unbiased, so the quantization
+error averages out over ranks and steps instead of flushing the same small
+components every time): compressed reduction number ``c`` of this wrapper,
+counted from construction, uses the seed ``compression_seed + c``, which is
+the same on all ranks because buckets reduce in a fixed order.
 """
 
 from typing import Dict, List, Optional
@@ -58,21 +63,25 @@ class DistributedDataParallel(torch.nn.Module):
     def __init__(self, module: torch.nn.Module, comm=None,
                  bucket_cap_mb: int = 128, average: bool = True,
                  find_unused_parameters: bool = False,
-                 grad_compression: Optional[str] = None):
+                 grad_compression: Optional[str] = None,
+                 compression_seed: int = 0):
         super().__init__()
-        if grad_compression not in (None, "mxfp8"):
+        if grad_compression not in (None, "mxfp8", "mxfp8-sr"):
             raise ValueError(
-                "mpi4torch_amd DDP: grad_compression must be None or "
-                f"'mxfp8', got {grad_compression!r}")
+                "mpi4torch_amd DDP: grad_compression must be None, 'mxfp8' "
+                f"or 'mxfp8-sr', got {grad_compression!r}")
         if grad_compression is not None:
             for n, p in module.named_parameters():
                 if p.requires_grad and p.dtype not in (
                         torch.float32, torch.bfloat16, torch.float16):
                     raise TypeError(
-                        "mpi4torch_amd DDP: grad_compression='mxfp8' needs "
+                        f"mpi4torch_amd DDP: grad_compression="
+                        f"{grad_compression!r} needs "
                         "float32, bfloat16 or float16 parameters; "
                         f"{n} is {p.dtype}")
         self.grad_compression = grad_compression
+        self.compression_seed = int(compression_seed)
+        self._compressed_reductions = 0
         self.module = module
         self.comm = comm if comm is not None else m4a.COMM_WORLD
         self.average = average
@@ -200,6 +209,15 @@ class DistributedDataParallel(torch.nn.Module):
             q.grad.copy_(reduced[off : off + n].view_as(q.grad))
             off += n
 
+    def _allreduce_compressed(self, flat):
+        """One bucket over the mxfp8 wire; under "mxfp8-sr" with the next
+        seed of this wrapper."""
+        seed = None
+        if self.grad_compression == "mxfp8-sr":
+            seed = self.compression_seed + self._compressed_reductions
+        self._compressed_reductions += 1
+        return self.comm.AllreduceCompressed(flat, m4a.MPI_SUM, seed)
+
     def _sync_compressed(self):
         """grad_compression path without unused parameters: every parameter
         must have fired (nothing was launched eagerly, so a missing gradient
@@ -224,8 +242,7 @@ class DistributedDataParallel(torch.nn.Module):
             for b in self._buckets:
                 flat = torch.cat(
                     [q.grad.reshape(-1) for q in b.params]).contiguous()
-                self._scatter_back(
-                    b.params, self.comm.AllreduceCompressed(flat, m4a.MPI_SUM))
+                self._scatter_back(b.params, self._allreduce_compressed(flat))
 
     def _sync_with_unused(self):
         """find_unused_parameters path: agree on the globally-used set,
@@ -256,8 +273,7 @@ class DistributedDataParallel(torch.nn.Module):
                 if self.grad_compression is not None:
                     # the vote above stays uncompressed; the buckets travel
                     # as mxfp8 (blocking, in bucket order)
-                    self._scatter_back(
-                        bp, self.comm.AllreduceCompressed(flat, m4a.MPI_SUM))
+                    self._scatter_back(bp, self._allreduce_compressed(flat))
                     continue
                 handles.append((b, bp, self.comm.Iallreduce(flat, m4a.MPI_SUM)))
             for b, bp, h in handles:

@@ -29,7 +29,9 @@ variant, so nothing is prefetched for such a model: the gather happens in
 materialize(). ``grad_compression="mxfp8"`` reduces every unit's gradient
 with the blocking ReducescatterCompressed as soon as the unit's backward is
 done, in place of the non-blocking Ireducescatter; the reduced shard is kept
-until finish_backward(). Neither option changes shard_len, so sharded
+until finish_backward(). ``grad_compression="mxfp8-sr"`` is the same with
+stochastic rounding, reduction number ``c`` of the wrapper under the seed
+``compression_seed + c``. Neither option changes shard_len, so sharded
 checkpoints stay interchangeable.
 """
 
@@ -43,8 +45,11 @@ import mpi4torch_amd as m4a
 class _Unit:
     def __init__(self, module: torch.nn.Module, comm, master_dtype=None,
                  param_compression: Optional[str] = None,
-                 grad_compression: Optional[str] = None):
+                 grad_compression: Optional[str] = None,
+                 next_seed=None):
         self.module = module
+        # "mxfp8-sr": the wrapper's counter of compressed reductions
+        self.next_seed = next_seed
         self.comm = comm
         self.param_compression = param_compression
         self.grad_compression = grad_compression
@@ -64,7 +69,8 @@ class _Unit:
                                      torch.float16)):
             raise ValueError(
                 "mpi4torch_amd FSDP: param_compression/grad_compression="
-                "'mxfp8' needs a float32, bfloat16 or float16 unit; this "
+                f"{param_compression or grad_compression!r} needs a float32, "
+                "bfloat16 or float16 unit; this "
                 f"unit's flat buffer is {p0.dtype}")
         with torch.no_grad():
             flat = torch.zeros(self.padded, dtype=p0.dtype, device=p0.device)
@@ -150,7 +156,9 @@ class _Unit:
             off += n
         if self.comm.size > 1 and self.grad_compression is not None:
             # blocking: stream-ordered on GPU, host-blocking on gloo
-            self.grad_reduced = self.comm.ReducescatterCompressed(gflat, 0)
+            seed = self.next_seed() if self.next_seed is not None else None
+            self.grad_reduced = self.comm.ReducescatterCompressed(gflat, 0,
+                                                                  seed)
         elif self.comm.size > 1:
             self.grad_handle = self.comm.Ireducescatter(gflat, m4a.MPI_SUM)
         else:
@@ -177,16 +185,21 @@ class FullyShardedDataParallel(torch.nn.Module):
                  comm=None, average: bool = True, master_dtype=None,
                  prefetch: int = 1,
                  param_compression: Optional[str] = None,
-                 grad_compression: Optional[str] = None):
+                 grad_compression: Optional[str] = None,
+                 compression_seed: int = 0):
         super().__init__()
-        for opt, val in (("param_compression", param_compression),
-                         ("grad_compression", grad_compression)):
-            if val not in (None, "mxfp8"):
-                raise ValueError(
-                    f"mpi4torch_amd FSDP: {opt} must be None or 'mxfp8', "
-                    f"got {val!r}")
+        if param_compression not in (None, "mxfp8"):
+            raise ValueError(
+                "mpi4torch_amd FSDP: param_compression must be None or "
+                f"'mxfp8', got {param_compression!r}")
+        if grad_compression not in (None, "mxfp8", "mxfp8-sr"):
+            raise ValueError(
+                "mpi4torch_amd FSDP: grad_compression must be None, 'mxfp8' "
+                f"or 'mxfp8-sr', got {grad_compression!r}")
         self.param_compression = param_compression
         self.grad_compression = grad_compression
+        self.compression_seed = int(compression_seed)
+        self._compressed_reductions = 0
         self.module = module
         self.comm = comm if comm is not None else m4a.COMM_WORLD
         self.average = average
@@ -226,7 +239,7 @@ class FullyShardedDataParallel(torch.nn.Module):
                     )
                 seen[p] = name
         self._units = [_Unit(m, self.comm, master_dtype, param_compression,
-                             grad_compression)
+                             grad_compression, self._next_compression_seed)
                        for m in unit_modules]
         self._by_module = {u.module: u for u in self._units}
         self._by_param = {p: u for u in self._units for p in u.params}
@@ -242,6 +255,17 @@ class FullyShardedDataParallel(torch.nn.Module):
             u.free()
 
     # ---- hooks -----------------------------------------------------------
+    def _next_compression_seed(self):
+        """The seed of the next compressed gradient reduction: None under
+        "mxfp8" (round to nearest), compression_seed + c under "mxfp8-sr",
+        c counting this wrapper's compressed reductions since construction
+        (units reduce in a fixed order, so c agrees on all ranks)."""
+        c = self._compressed_reductions
+        self._compressed_reductions += 1
+        if self.grad_compression == "mxfp8-sr":
+            return self.compression_seed + c
+        return None
+
     def _pre_forward(self, module, inputs):
         u = self._by_module[module]
         u.materialize()

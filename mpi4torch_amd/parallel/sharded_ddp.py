@@ -18,7 +18,9 @@ with the blocking ReducescatterCompressed (block-scaled fp8 wire, 33/32
 byte per element, every value quantized once) as soon as the bucket fills,
 in place of the non-blocking Ireducescatter; the reduced shard is kept until
 step(). Bucket layout and shard_len do not depend on the setting, so
-sharded checkpoints stay interchangeable.
+sharded checkpoints stay interchangeable. ``grad_compression="mxfp8-sr"``
+is the same with stochastic rounding, compressed reduction number ``c`` of
+the wrapper under the seed ``compression_seed + c``.
 """
 
 from typing import List, Optional
@@ -43,21 +45,24 @@ class ShardedDataParallel(torch.nn.Module):
     def __init__(self, module: torch.nn.Module, optimizer_cls, comm=None,
                  bucket_cap_mb: int = 64, average: bool = True,
                  master_dtype=None, grad_compression: Optional[str] = None,
-                 **optim_kwargs):
+                 compression_seed: int = 0, **optim_kwargs):
         super().__init__()
-        if grad_compression not in (None, "mxfp8"):
+        if grad_compression not in (None, "mxfp8", "mxfp8-sr"):
             raise ValueError(
                 "mpi4torch_amd ShardedDataParallel: grad_compression must "
-                f"be None or 'mxfp8', got {grad_compression!r}")
+                f"be None, 'mxfp8' or 'mxfp8-sr', got {grad_compression!r}")
         if grad_compression is not None:
             for n, p in module.named_parameters():
                 if p.requires_grad and p.dtype not in (
                         torch.float32, torch.bfloat16, torch.float16):
                     raise TypeError(
                         "mpi4torch_amd ShardedDataParallel: "
-                        "grad_compression='mxfp8' needs float32, bfloat16 "
+                        f"grad_compression={grad_compression!r} needs "
+                        "float32, bfloat16 "
                         f"or float16 parameters; {n} is {p.dtype}")
         self.grad_compression = grad_compression
+        self.compression_seed = int(compression_seed)
+        self._compressed_reductions = 0
         self.module = module
         self.comm = comm if comm is not None else m4a.COMM_WORLD
         self.average = average
@@ -140,7 +145,15 @@ class ShardedDataParallel(torch.nn.Module):
                     q.grad = None  # ZeRO-2: full grads freed immediately
                 if P > 1 and self.grad_compression is not None:
                     # blocking: stream-ordered on GPU, host-blocking on gloo
-                    b.reduced = self.comm.ReducescatterCompressed(flat, 0)
+                    # "mxfp8-sr": reduction number c of this wrapper rounds
+                    # stochastically under the seed compression_seed + c
+                    seed = None
+                    if self.grad_compression == "mxfp8-sr":
+                        seed = (self.compression_seed
+                                + self._compressed_reductions)
+                    self._compressed_reductions += 1
+                    b.reduced = self.comm.ReducescatterCompressed(flat, 0,
+                                                                  seed)
                 else:
                     b.handle = (self.comm.Ireducescatter(flat, m4a.MPI_SUM)
                                 if P > 1 else None)

@@ -92,10 +92,10 @@ class TracedCommunicator:
         return self._record("Allreduce", tensor,
                             lambda: self._comm.Allreduce(tensor, op))
 
-    def AllreduceCompressed(self, tensor, op=2):
+    def AllreduceCompressed(self, tensor, op=2, seed=None):
         return self._record(
             "AllreduceCompressed", tensor,
-            lambda: self._comm.AllreduceCompressed(tensor, op))
+            lambda: self._comm.AllreduceCompressed(tensor, op, seed))
 
     def Bcast_(self, tensor, root):
         return self._record("Bcast_", tensor,
@@ -129,10 +129,10 @@ class TracedCommunicator:
             "Reducescatter", tensor,
             lambda: self._comm.Reducescatter(tensor, axis, numelem))
 
-    def ReducescatterCompressed(self, tensor, axis=0):
+    def ReducescatterCompressed(self, tensor, axis=0, seed=None):
         return self._record(
             "ReducescatterCompressed", tensor,
-            lambda: self._comm.ReducescatterCompressed(tensor, axis))
+            lambda: self._comm.ReducescatterCompressed(tensor, axis, seed))
 
     def AllgatherCompressed(self, tensor, axis=0):
         return self._record(

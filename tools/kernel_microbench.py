@@ -12,6 +12,7 @@ reported GB/s counts actual bytes touched. Run on an MI355X box:
     python tools/kernel_microbench.py --mx8-segments            # only that part
     python tools/kernel_microbench.py --mx8-combine             # only that part
     python tools/kernel_microbench.py --mx8-weighted            # only that part
+    python tools/kernel_microbench.py --mx8-sr    # stochastic rounding vs nearest
 
 The mxfp8 section times the three codec kernels and, in the same run and
 alternating with it, the sibling fp8_reduce kernel at the same P and n, so
@@ -649,6 +650,52 @@ def mx8_weighted_section(repeats=5):
               f"{min(other)/med(other):.3f}-{max(other)/med(other):.3f}",
               flush=True)
 
+
+def mx8_sr_section(repeats=5):
+    """The stochastic-rounding kernels against their round-to-nearest
+    siblings, alternating in the same run, at the shapes of mx8_section (the
+    two sides move the same bytes)."""
+    C = m._C
+    NQ = 256 << 20
+    med = lambda v: sorted(v)[len(v) // 2]
+
+    def versus(tag, rne, sr, nbytes):
+        t_rne, t_sr = [], []
+        for _ in range(repeats):
+            t_rne.append(timeit(rne))
+            t_sr.append(timeit(sr))
+        for name, t in ((tag, t_rne), (tag.replace("mx8_", "mx8_sr_"), t_sr)):
+            print(f"{name:34s} {med(t)*1e3:9.1f} us  "
+                  f"{nbytes/med(t)/1e6:8.1f} GB/s  (min {min(t)*1e3:.1f} max "
+                  f"{max(t)*1e3:.1f} us, {repeats} repeats)", flush=True)
+        print(f"  sr / rne time ratio {med(t_sr)/med(t_rne):.3f}, rne spread "
+              f"{min(t_rne)/med(t_rne):.3f}-{max(t_rne)/med(t_rne):.3f}",
+              flush=True)
+
+    for dtype, tag in ((torch.float32, "fp32"), (torch.bfloat16, "bf16")):
+        x = torch.randn(NQ, device="cuda")
+        x.view(-1, 32).mul_(torch.rand(NQ // 32, 1, device="cuda"))
+        x = x.to(dtype)
+        versus(f"mx8_quantize {tag} N={NQ>>20}Mi",
+               lambda: C._mx8_quantize(x),
+               lambda: C._mx8_quantize_sr(x, 1, 0, 0, 0),
+               NQ * x.element_size() + 33 * NQ // 32)
+        del x
+    src = torch.randn(P, N, device="cuda") * 0.2
+    qs = [C._mx8_quantize(src[r]) for r in range(P)]
+    pay = torch.stack([q[0] for q in qs])
+    sc = torch.stack([q[1] for q in qs])
+    del src, qs
+    versus(f"mx8_reduce P={P} n={N>>25}Mi groups",
+           lambda: C._mx8_reduce(pay, sc),
+           lambda: C._mx8_reduce_sr(pay, sc, 1, 1, 0, 0),
+           (P + 1) * (33 * N // 32))
+
+
+if "--mx8-sr" in sys.argv:
+    mx8_sr_section()
+    dist.destroy_process_group()
+    sys.exit(0)
 
 if "--mx8-weighted" in sys.argv:
     mx8_weighted_section()
