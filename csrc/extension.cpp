@@ -57,6 +57,7 @@ static auto communicator_class =
         .def("ReducescatterCompressedStochastic",
              &Communicator::ReducescatterCompressedStochastic)
         .def("AllgatherCompressed", &Communicator::AllgatherCompressed)
+        .def("AllgatherCompressedFp4", &Communicator::AllgatherCompressedFp4)
         .def("AlltoallCompressed", &Communicator::AlltoallCompressed)
         .def("Scatter", &Communicator::Scatter)
         .def("Alltoall", &Communicator::Alltoall)
@@ -138,6 +139,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out") = c10::optional<at::Tensor>());
   m.def("_mx8_dequantize_blocks", &m4a::debug_mx8_dequantize_blocks,
         py::arg("payload"), py::arg("scales"), py::arg("rows"),
+        py::arg("row_elems"), py::arg("dtype"),
+        py::arg("out") = c10::optional<at::Tensor>());
+  m.def("_mx4_quantize", &m4a::debug_mx4_quantize, py::arg("x"),
+        py::arg("payload_out") = c10::optional<at::Tensor>(),
+        py::arg("scales_out") = c10::optional<at::Tensor>());
+  m.def("_mx4_dequantize_blocks", &m4a::debug_mx4_dequantize_blocks,
+        py::arg("payload"), py::arg("scales"), py::arg("P"), py::arg("rows"),
         py::arg("row_elems"), py::arg("dtype"),
         py::arg("out") = c10::optional<at::Tensor>());
   m.def("_mx8_quantize_blocks", &m4a::debug_mx8_quantize_blocks,

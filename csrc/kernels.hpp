@@ -174,6 +174,27 @@ void launch_mx8_quantize_blocks(const void* in, void* payload, void* scales,
                                 int nblocks, int64_t rows, int64_t row_elems,
                                 int dtype, hipStream_t stream);
 
+// mxfp4 codec, the second wire of AllgatherCompressed (csrc/mx8_kernels.hip):
+// groups of 32 consecutive elements -> 16 payload bytes of OCP e2m1 nibbles
+// (element 2j in the low nibble of byte j, 2j+1 in the high one) + one E8M0
+// scale byte (255 = non-finite group), 17/32 byte per element. The rule is
+// defined by the torch composite in csrc/ops.cpp (mx4_quantize_groups); the
+// kernels match it byte for byte. dtype codes as above.
+//
+// Quantize n_elems elements: payload gets ceil(n/32)*16 bytes (the partial
+// last group is zero-padded), scales ceil(n/32) bytes.
+void launch_mx4_quantize(const void* in, void* payload, void* scales,
+                         int64_t n_elems, int dtype, hipStream_t stream);
+// The allgather tail, launch_mx8_dequantize_blocks on the mxfp4 wire:
+// payload [nblocks][Gb*16], scales [nblocks][Gb], Gb = ceil(rows*row_elems/32)
+// out [rows][nblocks][row_elems] contiguous, of `dtype`:
+//   out[b][r][j] = cast(dq(block r))[b*row_elems + j]
+// Writes exactly rows*nblocks*row_elems elements. nblocks <= 65535 (grid.y).
+void launch_mx4_dequantize_blocks(const void* payload, const void* scales,
+                                  void* out, int nblocks, int64_t rows,
+                                  int64_t row_elems, int dtype,
+                                  hipStream_t stream);
+
 // One segment of the variable-count codec kernels below: `count` slices of
 // the stream side starting at slice `displ`, whose mxfp8 stream starts at
 // group `goff` (payload byte 32*goff, scale byte goff).

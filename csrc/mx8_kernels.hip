@@ -73,6 +73,9 @@
 //                themselves only pick the stream that grid.y names;
 //   sum_copies : the rank-order sum of reduce and reduce_to;
 //   SegCursor  : the (b, c, a) walk of the two segments twins.
+// The mxfp4 wire of AllgatherCompressed (e2m1 nibbles under the same groups
+// and scale byte) has its quantize and dequantize_blocks kernels at the end
+// of this file, with its rule.
 // On the host, by_dtype / by_width / by_width_mode turn the run-time dtype,
 // index width and segment mode into template arguments, grid2d is the capped
 // 2-D grid, and launch_segments_t is both segments launchers.
@@ -2160,6 +2163,383 @@ void launch_mx8_dequantize(const void* payload, const void* scales, void* out,
   if (n_elems <= 0) return;
   by_dtype(dtype, [&](auto k) {
     launch_dequantize_t<k>(payload, scales, out, n_elems, stream);
+  });
+}
+
+// ===========================================================================
+// mxfp4: the second wire of AllgatherCompressed
+// ===========================================================================
+//
+// The family's rule with OCP e2m1 in place of e4m3 (normative in csrc/ops.cpp,
+// mx4_quantize_groups / mx4_dequantize_groups): a group of 32 elements is 16
+// payload bytes (element 2j in the low nibble of byte j, 2j+1 in the high
+// one) plus the E8M0 scale byte, 17/32 byte per element. A nibble is
+// sign<<3 | code, code 0..7 = 0, 0.5, 1, 1.5, 2, 3, 4, 6. With amax = m*2^k,
+// m in [0.5,1): E = k-3 if m <= 0.75 else k-2, clamped to [-127,127], so
+// amax*2^-E <= 6 and the conversion cannot saturate.
+//
+// The conversions are the gfx950 packed converts (v_cvt_scalef32_pk_fp4_f32,
+// v_cvt_scalef32_pk_f32_fp4) at scale 1: the shared exponent is applied by
+// ldexpf, exact and defined at E = -127, where the instruction's own scale
+// operand would be an fp32 subnormal. Elements met one by one (heads, tails,
+// nibble-shifted chunks of the general twin) are decoded in integer
+// arithmetic, mx4_nibble_to_f32.
+//
+// Three kernels and the twins of the first and last, all 256 threads,
+// grid-stride, no LDS:
+//   quantize  : 8 elements per lane, 4 lanes per group, for every dtype (one
+//               16-byte load for the 16-bit dtypes, two for fp32); the amax
+//               crosses the group by two xor-shuffles; a lane stores one
+//               packed payload dword, a wave 256 contiguous bytes; the
+//               wave's 16 scale bytes leave through store_scales<4>. The
+//               loop covers ALL G*4 lane slots: elements past N are zeros
+//               and store the zero padding, so there is no scalar tail.
+//   dequantize_blocks : the allgather tail, mx8_dequantize_blocks_kernel's
+//               geometry (grid.y = block, BlockMap): one 16-byte store per
+//               lane, fed by a payload dword (16-bit dtypes, 8 elements) or
+//               two payload bytes (fp32, 4 elements).
+//   its general twin : mx8_dequantize_blocks_kernel_shifted's split of every
+//               (block, row) segment at the 16-byte boundaries of the
+//               destination; a chunk may start at an odd element of the
+//               block, i.e. in the middle of a payload byte (see there).
+
+namespace {
+
+typedef float v2f __attribute__((ext_vector_type(2)));
+
+__device__ inline int mx4_scale_byte(unsigned amax_bits, int* E) {
+  if (amax_bits >= kInfBits) {
+    *E = 0;
+    return 255;
+  }
+  const int e = (int)(amax_bits >> 23);
+  const unsigned f = amax_bits & 0x7fffffu;
+  int ex;
+  if (amax_bits == 0) {
+    ex = 0;
+  } else if (e == 0) {
+    ex = -127;  // fp32 subnormal amax: k <= -126, k-2 clamps
+  } else {
+    // amax = 1.f * 2^(e-127) = m * 2^(e-126); m <= 0.75 <=> f <= 0x400000
+    ex = (e - 126) - (f <= 0x400000u ? 3 : 2);
+    if (ex < -127) ex = -127;
+  }
+  *E = ex;
+  return ex + 127;
+}
+
+// byte SEL of `old` <- the e2m1 nibbles of a (low) and b (high), RNE
+template <int SEL>
+__device__ inline unsigned mx4_cvt_pk(unsigned old, float a, float b) {
+  return __builtin_amdgcn_cvt_scalef32_pk_fp4_f32(old, a, b, 1.0f, SEL);
+}
+
+// a lane's 8 elements under the shared exponent E -> its payload dword
+__device__ inline unsigned mx4_quant8(const float (&x)[8], int E) {
+  unsigned w = 0;
+  w = mx4_cvt_pk<0>(w, ldexpf(x[0], -E), ldexpf(x[1], -E));
+  w = mx4_cvt_pk<1>(w, ldexpf(x[2], -E), ldexpf(x[3], -E));
+  w = mx4_cvt_pk<2>(w, ldexpf(x[4], -E), ldexpf(x[5], -E));
+  w = mx4_cvt_pk<3>(w, ldexpf(x[6], -E), ldexpf(x[7], -E));
+  return w;
+}
+
+// the low N (4 or 8) nibbles of w as their grid values (scale 1)
+template <int N>
+__device__ inline void mx4_decode(unsigned w, float (&v)[N]) {
+  const v2f a = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, 1.0f, 0);
+  const v2f b = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, 1.0f, 1);
+  v[0] = a[0], v[1] = a[1], v[2] = b[0], v[3] = b[1];
+  if constexpr (N == 8) {
+    const v2f c = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, 1.0f, 2);
+    const v2f d = __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(w, 1.0f, 3);
+    v[4] = c[0], v[5] = c[1], v[6] = d[0], v[7] = d[1];
+  }
+}
+
+__device__ inline float mx4_scaled(float v, int sb) {
+  return sb == 255 ? __uint_as_float(kQNaNBits) : ldexpf(v, sb - 127);
+}
+
+// One nibble in integer arithmetic: code 1 is 0.5, code c >= 2 is
+// (1 + (c&1)/2) * 2^((c>>1) - 1); bit 3 is the sign, kept on zero.
+__device__ inline float mx4_nibble_to_f32(unsigned nib) {
+  const unsigned c = nib & 7u;
+  const unsigned mag = c == 0   ? 0u
+                       : c == 1 ? 0x3f000000u
+                                : ((126u + (c >> 1)) << 23) | ((c & 1u) << 22);
+  return __uint_as_float(mag | ((nib & 8u) << 28));
+}
+
+__device__ inline float mx4_dequant(unsigned nib, int sb) {
+  return mx4_scaled(mx4_nibble_to_f32(nib), sb);
+}
+
+// ---- quantize -----------------------------------------------------------
+
+// Lane slot i's elements [8i, 8i+8) of the N-element stream; zeros past N.
+// Only the one slot that straddles N reads element by element.
+template <int K>
+__device__ inline void mx4_load8(const void* __restrict__ in, long long i,
+                                 long long N, float (&x)[8]) {
+  using T = typename Elem<K>::type;
+  const long long e0 = i * 8;
+  if (e0 + 8 <= N) {
+    if constexpr (K == kF32) {
+      const v4u a =
+          __builtin_nontemporal_load(reinterpret_cast<const v4u*>(in) + 2 * i);
+      const v4u b = __builtin_nontemporal_load(
+          reinterpret_cast<const v4u*>(in) + 2 * i + 1);
+      for (int d = 0; d < 4; ++d) {
+        x[d] = __uint_as_float(a[d]);
+        x[4 + d] = __uint_as_float(b[d]);
+      }
+    } else {
+      unpack16<K, 8>(
+          __builtin_nontemporal_load(reinterpret_cast<const v4u*>(in) + i), x);
+    }
+  } else {
+    for (int k = 0; k < 8; ++k) {
+      x[k] = e0 + k < N
+                 ? elem_to_f32<K>(reinterpret_cast<const T*>(in)[e0 + k])
+                 : 0.0f;
+    }
+  }
+}
+
+template <int K>
+__global__ __launch_bounds__(256) void mx4_quantize_kernel(
+    const void* __restrict__ in, u8* __restrict__ pay, u8* __restrict__ sc,
+    long long G, long long N) {
+  const long long slots = G * 4;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  const int lane = threadIdx.x & 63;
+  // wave-uniform trip count: the shuffles below and in store_scales need
+  // every lane present; slots is a multiple of 4, so a group is never cut
+  for (long long i0 = (long long)blockIdx.x * blockDim.x + (threadIdx.x & ~63);
+       i0 < slots; i0 += stride) {
+    const long long i = i0 + lane;
+    const bool act = i < slots;
+    float x[8];
+    if (act) {
+      mx4_load8<K>(in, i, N, x);
+    } else {
+      for (int k = 0; k < 8; ++k) x[k] = 0.0f;
+    }
+    unsigned a = amax_bits_of(x);
+    for (int m = 1; m < 4; m <<= 1) {
+      const unsigned o = (unsigned)__shfl_xor((int)a, m);
+      a = o > a ? o : a;
+    }
+    int E;
+    const int sb = mx4_scale_byte(a, &E);
+    if (act) {
+      __builtin_nontemporal_store(sb == 255 ? 0u : mx4_quant8(x, E),
+                                  reinterpret_cast<unsigned*>(pay) + i);
+    }
+    store_scales<4>(sc, i0 / 4, G, sb, lane);
+  }
+}
+
+// One thread per group, any alignment of the input and payload bases.
+template <int K>
+__global__ __launch_bounds__(256) void mx4_quantize_kernel_scalar(
+    const void* __restrict__ in, u8* __restrict__ pay, u8* __restrict__ sc,
+    long long G, long long N) {
+  using T = typename Elem<K>::type;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < G;
+       g += stride) {
+    const T* p = reinterpret_cast<const T*>(in) + g * 32;
+    const long long left = N - g * 32;
+    float x[32];
+    for (int k = 0; k < 32; ++k) {
+      x[k] = k < left ? elem_to_f32<K>(p[k]) : 0.0f;
+    }
+    int E;
+    const int sb = mx4_scale_byte(amax_bits_of(x), &E);
+    for (int j = 0; j < 16; ++j) {
+      pay[g * 16 + j] =
+          sb == 255 ? (u8)0
+                    : (u8)mx4_cvt_pk<0>(0u, ldexpf(x[2 * j], -E),
+                                        ldexpf(x[2 * j + 1], -E));
+    }
+    sc[g] = (u8)sb;
+  }
+}
+
+// ---- dequantize_blocks (the allgather tail) ------------------------------
+//
+// pay [nblocks][Gb*16], sc [nblocks][Gb], Gb = ceil(L/32), L = rows*row_elems
+// -> out [rows][nblocks][row_elems]. Vector body: one 16-byte store per lane,
+// EPL = 8 elements (a payload dword) for the 16-bit dtypes and 4 (a 2-byte
+// payload load) for fp32, where two stores per lane measured 19 % slower
+// (doc/kernels.md section 5). It requires row_elems % EPL == 0, a 16-byte
+// aligned output and an EPL/2-byte aligned payload. Chunk i of the block
+// (scale byte i*EPL/32: the group runs over the block-flat index and may
+// straddle rows) lies inside one row; BlockMap gives its place in 16-byte
+// units. L % EPL == 0, so the partial last group is whole chunks and nothing
+// past element L is written.
+template <int K> constexpr int kMx4EPL = K == kF32 ? 4 : 8;
+
+template <int K, typename I>
+__global__ __launch_bounds__(256) void mx4_dequantize_blocks_kernel(
+    const u8* __restrict__ pay, const u8* __restrict__ sc,
+    void* __restrict__ out, long long Gb, I chunks, I cpr,
+    long long nblocks) {
+  using W = std::conditional_t<K == kF32, unsigned short, unsigned>;
+  constexpr int EPL = kMx4EPL<K>;
+  const long long r = blockIdx.y;
+  const W* __restrict__ bp = reinterpret_cast<const W*>(pay + r * Gb * 16);
+  const u8* __restrict__ bs = sc + r * Gb;
+  const BlockMap<I> map{r, nblocks, cpr};
+  const I stride = (I)gridDim.x * blockDim.x;
+  for (I i = (I)blockIdx.x * blockDim.x + threadIdx.x; i < chunks;
+       i += stride) {
+    const int sb = bs[i / (32 / EPL)];
+    float x[EPL];
+    mx4_decode<EPL>(__builtin_nontemporal_load(bp + i), x);
+    for (int k = 0; k < EPL; ++k) x[k] = mx4_scaled(x[k], sb);
+    __builtin_nontemporal_store(pack16<K, EPL>(x),
+                                reinterpret_cast<v4u*>(out) + map(i));
+  }
+}
+
+// General twin: any row length, any alignment of the payload and output
+// bases. The split and the lane slots are those of
+// mx8_dequantize_blocks_kernel_shifted: per (block, row) segment up to EPL-1
+// head elements, whole aligned 16-byte chunks of EPL elements, up to EPL-1
+// tail elements; row_elems/EPL + 2 slots per row. New with nibbles: a chunk's
+// first element src may be odd within the block, its EPL nibbles then start
+// in the high half of payload byte src/2 and end in the low half of byte
+// src/2 + EPL/2. The window is the EPL/2 bytes from src/2 on (one unaligned
+// load) plus, for an odd src only, the byte after them, shifted right by the
+// nibble phase. The chunk may belong to two groups, hence two scale bytes.
+template <int K, typename I>
+__global__ __launch_bounds__(256) void mx4_dequantize_blocks_kernel_shifted(
+    const u8* __restrict__ pay, const u8* __restrict__ sc,
+    void* __restrict__ out, long long Gb, long long row_elems, I slots,
+    I total, long long nblocks) {
+  using T = typename Elem<K>::type;
+  using W = std::conditional_t<K == kF32, unsigned short, unsigned>;
+  constexpr int EPL = kMx4EPL<K>;
+  const long long r = blockIdx.y;
+  const u8* __restrict__ bp = pay + r * Gb * 16;
+  const u8* __restrict__ bs = sc + r * Gb;
+  auto nibble = [&](long long e) {
+    return (unsigned)(bp[e >> 1] >> (4 * (int)(e & 1))) & 15u;
+  };
+  const I stride = (I)gridDim.x * blockDim.x;
+  for (I i = (I)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += stride) {
+    const I b = i / slots;
+    const long long k = (long long)(i - b * slots);
+    T* d = reinterpret_cast<T*>(out) +
+           ((long long)b * nblocks + r) * row_elems;  // the segment
+    const long long s0 = (long long)b * row_elems;    // its block-flat start
+    long long head =
+        (long long)(((16 - (reinterpret_cast<uintptr_t>(d) & 15)) & 15) /
+                    sizeof(T));
+    if (head > row_elems) head = row_elems;
+    const long long nchunks = (row_elems - head) / EPL;
+    if (k < nchunks) {
+      const long long e = head + k * EPL;
+      const long long src = s0 + e;
+      const int ph = (int)(src & 1);
+      const u8* p = bp + (src >> 1);
+      W lo;
+      __builtin_memcpy(&lo, p, EPL / 2);
+      unsigned long long win = lo;
+      if (ph) win |= (unsigned long long)p[EPL / 2] << (4 * EPL);
+      win >>= 4 * ph;
+      const long long g0 = src >> 5;
+      const int sb0 = bs[g0];
+      const int sb1 = bs[(src + EPL - 1) >> 5];
+      float x[EPL];
+      mx4_decode<EPL>((unsigned)win, x);
+      for (int t = 0; t < EPL; ++t) {
+        x[t] = mx4_scaled(x[t], ((src + t) >> 5) == g0 ? sb0 : sb1);
+      }
+      __builtin_nontemporal_store(pack16<K, EPL>(x),
+                                  reinterpret_cast<v4u*>(d + e));
+    } else if (k >= (long long)slots - 2) {
+      // head [0, head) or tail [head + nchunks*EPL, row_elems): fewer than
+      // EPL elements each, stored one by one
+      const bool is_head = k == (long long)slots - 2;
+      const long long lo = is_head ? 0 : head + nchunks * EPL;
+      const long long hi = is_head ? head : row_elems;
+      for (long long e = lo; e < hi; ++e) {
+        d[e] = f32_to_elem<K>(mx4_dequant(nibble(s0 + e), bs[(s0 + e) >> 5]));
+      }
+    }
+  }
+}
+
+template <int K>
+void launch_mx4_quantize_t(const void* in, u8* pay, u8* sc, int64_t N,
+                           hipStream_t stream) {
+  const long long G = (N + 31) / 32;
+  if (aligned(in, 16) && aligned(pay, 4)) {
+    hipLaunchKernelGGL((mx4_quantize_kernel<K>), dim3(grid_for(G * 4)),
+                       dim3(256), 0, stream, in, pay, sc, G, (long long)N);
+  } else {
+    hipLaunchKernelGGL((mx4_quantize_kernel_scalar<K>), dim3(grid_for(G)),
+                       dim3(256), 0, stream, in, pay, sc, G, (long long)N);
+  }
+}
+
+template <int K>
+void launch_mx4_dequantize_blocks_t(const u8* pay, const u8* sc, void* out,
+                                    int nblocks, int64_t rows,
+                                    int64_t row_elems, hipStream_t stream) {
+  const long long L = rows * row_elems;
+  const long long Gb = (L + 31) / 32;
+  // Every block's payload base is pay + r*Gb*16, so an aligned pay keeps all
+  // of them aligned; row_elems % EPL == 0 with an aligned out keeps every
+  // chunk's destination aligned.
+  constexpr int EPL = kMx4EPL<K>;
+  if (aligned(out, 16) && aligned(pay, EPL / 2) && row_elems % EPL == 0) {
+    const long long chunks = L / EPL;
+    const long long cpr = row_elems / EPL;
+    by_width(chunks, [&](auto i) {
+      using I = decltype(i);
+      hipLaunchKernelGGL((mx4_dequantize_blocks_kernel<K, I>),
+                         grid2d(chunks, nblocks), dim3(256), 0, stream, pay,
+                         sc, out, Gb, (I)chunks, (I)cpr, (long long)nblocks);
+    });
+  } else {
+    const long long slots = row_elems / EPL + 2;
+    const long long total = rows * slots;
+    by_width(total, [&](auto i) {
+      using I = decltype(i);
+      hipLaunchKernelGGL((mx4_dequantize_blocks_kernel_shifted<K, I>),
+                         grid2d(total, nblocks), dim3(256), 0, stream, pay, sc,
+                         out, Gb, (long long)row_elems, (I)slots, (I)total,
+                         (long long)nblocks);
+    });
+  }
+}
+
+} // namespace
+
+void launch_mx4_quantize(const void* in, void* payload, void* scales,
+                         int64_t n_elems, int dtype, hipStream_t stream) {
+  if (n_elems <= 0) return;
+  by_dtype(dtype, [&](auto k) {
+    launch_mx4_quantize_t<k>(in, static_cast<u8*>(payload),
+                             static_cast<u8*>(scales), n_elems, stream);
+  });
+}
+
+void launch_mx4_dequantize_blocks(const void* payload, const void* scales,
+                                  void* out, int nblocks, int64_t rows,
+                                  int64_t row_elems, int dtype,
+                                  hipStream_t stream) {
+  if (nblocks <= 0 || rows <= 0 || row_elems <= 0) return;
+  by_dtype(dtype, [&](auto k) {
+    launch_mx4_dequantize_blocks_t<k>(static_cast<const u8*>(payload),
+                                      static_cast<const u8*>(scales), out,
+                                      nblocks, rows, row_elems, stream);
   });
 }
 

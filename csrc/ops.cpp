@@ -1227,6 +1227,139 @@ Tensor mx8_allgather(Transport& tr, const Tensor& in, int64_t rows,
                                in.scalar_type());
 }
 
+// ------------------------- mxfp4 compressed allgather ----------------------
+//
+// The family's codec with OCP e2m1 in place of e4m3 (normative; the gfx950
+// kernels match this torch composite byte for byte): groups of 32 consecutive
+// elements of the flat tensor, each 16 payload bytes + one E8M0 scale byte.
+// Byte j of a group holds element 2j in its low nibble and element 2j+1 in
+// its high nibble; a nibble is sign<<3 | code, code 0..7 standing for
+// 0, 0.5, 1, 1.5, 2, 3, 4, 6.
+//   quantize : amax over |x| in fp32. Non-finite group -> scale 255, zero
+//              payload. amax == 0 -> E = 0. Else amax = m*2^k (frexp,
+//              m in [0.5,1)): E = k-3 if m <= 0.75 else k-2, clamped to
+//              [-127,127] — the smallest E with amax*2^-E <= 6. Scale byte
+//              E+127; nibble = RNE(x * 2^-E) onto the grid, ties to the code
+//              with an even low bit (never saturates); the sign bit is kept,
+//              also where the value rounds to zero.
+//   dequant  : value(code) * 2^E with sign (exact); scale 255 -> NaN group.
+
+// |y| <= 6 -> code 0..7: the count of the grid's seven rounding boundaries
+// that |y| passes. A tie goes up exactly where the upper code is even.
+Tensor mx4_codes(const Tensor& ay) {
+  return ay.gt(0.25).to(at::kByte) + ay.ge(0.75).to(at::kByte) +
+         ay.gt(1.25).to(at::kByte) + ay.ge(1.75).to(at::kByte) +
+         ay.gt(2.5).to(at::kByte) + ay.ge(3.5).to(at::kByte) +
+         ay.gt(5.0).to(at::kByte);
+}
+
+// xg: [G, 32] fp32 -> (payload [G, 16] u8, scales [G] u8)
+std::pair<Tensor, Tensor> mx4_quantize_groups(const Tensor& xg) {
+  auto finite = at::isfinite(xg).all(1);
+  auto amax = xg.abs().amax(1).masked_fill(finite.logical_not(), 0);
+  auto mk = at::frexp(amax);
+  auto m = std::get<0>(mk);
+  auto k = std::get<1>(mk).to(at::kInt);
+  auto E = k - at::where(m.le(0.75), at::full_like(k, 3), at::full_like(k, 2));
+  E = at::where(amax.eq(0), at::zeros_like(E), E).clamp(-127, 127);
+  auto scaled = xg * mx8_pow2(-E).unsqueeze(1);
+  auto nib = mx4_codes(scaled.abs()) + at::signbit(scaled).to(at::kByte) * 8;
+  nib = at::where(finite.unsqueeze(1), nib, at::zeros_like(nib))
+            .view({-1, 16, 2});
+  auto pay = nib.select(2, 0) + nib.select(2, 1) * 16;
+  auto sc = at::where(finite, E + 127, at::full_like(E, 255)).to(at::kByte);
+  return {pay.contiguous(), sc.contiguous()};
+}
+
+// payload [G, 16] u8, scales [G] u8 -> [G, 32] fp32
+Tensor mx4_dequantize_groups(const Tensor& pay, const Tensor& sc) {
+  auto nib = at::stack({pay.bitwise_and(15), pay.bitwise_right_shift(4)}, 2)
+                 .view({-1, 32});
+  auto grid = at::tensor({0.0f, 0.5f, 1.0f, 1.5f, 2.0f, 3.0f, 4.0f, 6.0f},
+                         pay.options().dtype(at::kFloat));
+  auto v = grid.index({nib.bitwise_and(7).to(at::kLong)});
+  v = at::where(nib.bitwise_and(8).ne(0), v.neg(), v);
+  auto E = (sc.to(at::kInt) - 127).clamp(-127, 127);
+  auto d = v * mx8_pow2(E).unsqueeze(1);
+  return at::where(sc.eq(255).unsqueeze(1),
+                   at::full_like(d, std::numeric_limits<float>::quiet_NaN()),
+                   d);
+}
+
+// flat contiguous x -> (payload [G*16] u8, scales [G] u8), G = ceil(N/32)
+std::pair<Tensor, Tensor> mx4_quantize(
+    const Tensor& x, const c10::optional<Tensor>& payload_out = c10::nullopt,
+    const c10::optional<Tensor>& scales_out = c10::nullopt) {
+  const int dt = mx8_dtype_code(x.scalar_type(), "mxfp4 compression");
+  const int64_t N = x.numel();
+  const int64_t G = (N + 31) / 32;
+  auto bopts = x.options().dtype(at::kByte);
+  auto pay = out_or_empty(payload_out, {G * 16}, bopts);
+  auto sc = out_or_empty(scales_out, {G}, bopts);
+  if (x.is_cuda()) {
+    launch_mx4_quantize(x.data_ptr(), pay.data_ptr(), sc.data_ptr(), N, dt,
+                        current_gpu_stream(x));
+    return {pay, sc};
+  }
+  auto padded = at::zeros({G * 32}, x.options().dtype(at::kFloat));
+  padded.narrow(0, 0, N).copy_(x.view({-1}));
+  auto ps = mx4_quantize_groups(padded.view({G, 32}));
+  if (!payload_out.has_value()) return {ps.first.view({-1}), ps.second};
+  pay.copy_(ps.first.view({-1}));
+  sc.copy_(ps.second);
+  return {pay, sc};
+}
+
+// mx8_dequantize_blocks on the mxfp4 wire: pay [P * Gb*16], sc [P * Gb] ->
+// [rows, P, row_elems] of `dtype`,
+//   out[b, r, j] = dq(block r)[b*row_elems + j].to(dtype)
+Tensor mx4_dequantize_blocks(const Tensor& pay, const Tensor& sc, int P,
+                             int64_t rows, int64_t row_elems,
+                             at::ScalarType dtype,
+                             const c10::optional<Tensor>& out_opt =
+                                 c10::nullopt) {
+  const int dt = mx8_dtype_code(dtype, "mxfp4 compression");
+  TORCH_CHECK(P >= 1 && P <= 65535,
+              "mpi4torch_amd: mx4_dequantize_blocks supports 1..65535 "
+              "blocks, got ", P);
+  auto out = out_or_empty(out_opt, {rows, (int64_t)P, row_elems},
+                          pay.options().dtype(dtype));
+  if (out.numel() == 0) return out;
+  if (pay.is_cuda()) {
+    launch_mx4_dequantize_blocks(pay.data_ptr(), sc.data_ptr(),
+                                 out.data_ptr(), P, rows, row_elems, dt,
+                                 current_gpu_stream(pay));
+    return out;
+  }
+  const int64_t L = rows * row_elems;
+  const int64_t Gb = (L + 31) / 32;
+  auto pv = pay.view({P, Gb, 16});
+  auto sv = sc.view({P, Gb});
+  for (int r = 0; r < P; ++r) {
+    auto d = mx4_dequantize_groups(pv[r], sv[r]).view({-1});
+    out.select(1, r).copy_(
+        d.narrow(0, 0, L).to(dtype).view({rows, row_elems}));
+  }
+  return out;
+}
+
+// mx8_allgather on the mxfp4 wire: one quantize, the two byte allgathers
+// (payload [P][Gb*16], scales [P][Gb]), the fused tail. The wire carries
+// (P-1)*17*ceil(L/32) bytes received per rank.
+Tensor mx4_allgather(Transport& tr, const Tensor& in, int64_t rows,
+                     int64_t row_elems) {
+  const int P = tr.size();
+  const int64_t Gb = (rows * row_elems + 31) / 32;
+  auto q = mx4_quantize(in.view({-1}));
+  auto bopts = in.options().dtype(at::kByte);
+  auto all_pay = at::empty({(int64_t)P * Gb * 16}, bopts);
+  auto all_sc = at::empty({(int64_t)P * Gb}, bopts);
+  tr.allgather_equal(q.first, all_pay);
+  tr.allgather_equal(q.second, all_sc);
+  return mx4_dequantize_blocks(all_pay, all_sc, P, rows, row_elems,
+                               in.scalar_type());
+}
+
 // `in`: contiguous, rows*P*row_elems elements seen as [rows, P, row_elems]
 // -> (payload [P, Gb*32], scales [P, Gb]), Gb = ceil(rows*row_elems/32).
 // The all-to-all head, normative here: block p is mx8_quantize of the
@@ -2733,8 +2866,13 @@ struct AllgatherCompressedBackward : public M4ANode {
 };
 } // namespace
 
-Tensor Communicator::AllgatherCompressed(const Tensor& input, int64_t axis) {
-  check_mx8_input("AllgatherCompressed", input);
+namespace {
+// Both wires; `fp4` selects mxfp4 (the backward is the mxfp8 reduce-scatter
+// either way: gradients do not go to fp4).
+Tensor allgather_compressed(Communicator& comm, const Tensor& input,
+                            int64_t axis, bool fp4) {
+  const char* who = fp4 ? "AllgatherCompressedFp4" : "AllgatherCompressed";
+  check_mx8_input(who, input);
   axis = at::maybe_wrap_dim(axis, input.dim());
   auto make_grad_fn = [&](auto comm) {
     return make_node<AllgatherCompressedBackward>(comm, axis);
@@ -2742,25 +2880,36 @@ Tensor Communicator::AllgatherCompressed(const Tensor& input, int64_t axis) {
   auto body = [&](Transport& tr, const Tensor& in,
                   const DeviceStager&) -> Tensor {
     const int P = tr.size();
-    // full path: quantize, 1-rank allgather, mx8_dequantize_blocks
+    // full path: quantize, 1-rank allgather, mx8/mx4_dequantize_blocks
     if (world1_shortcut(tr, in)) return fast_clone(in);
-    debug_check_axis_collective(group_name_, "AllgatherCompressed", in,
-                                {axis}, {axis});
+    debug_check_axis_collective(comm.group_name(), who, in, {axis}, {axis});
     const auto g = axis_geom(in, axis);
-    auto counts = host_allgather_int64(group_name_, g.axis);
+    auto counts = host_allgather_int64(comm.group_name(), g.axis);
     const bool equal = std::all_of(counts.begin(), counts.end(),
                                    [&](int64_t c) { return c == counts[0]; });
     TORCH_CHECK(equal,
-                "mpi4torch_amd: AllgatherCompressed requires equal counts: "
+                "mpi4torch_amd: ", who, " requires equal counts: "
                 "every rank's tensor must have the same size on axis ", axis,
                 " (this rank has ", g.axis, "); Allgather handles variable "
                 "counts");
     auto outsizes = in.sizes().vec();
     outsizes[axis] = g.axis * P;
     if (in.numel() == 0) return at::empty(outsizes, in.options());
-    return mx8_allgather(tr, in, g.before, g.axis * g.after).view(outsizes);
+    return (fp4 ? mx4_allgather(tr, in, g.before, g.axis * g.after)
+                : mx8_allgather(tr, in, g.before, g.axis * g.after))
+        .view(outsizes);
   };
-  return collective_frame(*this, input, make_grad_fn, body);
+  return collective_frame(comm, input, make_grad_fn, body);
+}
+} // namespace
+
+Tensor Communicator::AllgatherCompressed(const Tensor& input, int64_t axis) {
+  return allgather_compressed(*this, input, axis, false);
+}
+
+Tensor Communicator::AllgatherCompressedFp4(const Tensor& input,
+                                            int64_t axis) {
+  return allgather_compressed(*this, input, axis, true);
 }
 
 // ---------------------------------------------------------------------------
@@ -4322,6 +4471,56 @@ Tensor debug_mx8_dequantize_blocks(const Tensor& payload,
   return mx8_dequantize_blocks(
       pin, sin, P, rows, row_elems, dtype,
       out->narrow(0, 0, total).view({rows, (int64_t)P, row_elems}));
+}
+
+std::tuple<Tensor, Tensor> debug_mx4_quantize(
+    const Tensor& x, const c10::optional<Tensor>& payload_out,
+    const c10::optional<Tensor>& scales_out) {
+  auto flat = x.contiguous().view({-1});
+  TORCH_CHECK(payload_out.has_value() == scales_out.has_value(),
+              "debug_mx4_quantize: payload_out and scales_out go together");
+  if (!payload_out.has_value()) {
+    auto ps = mx4_quantize(flat);
+    return std::make_tuple(ps.first, ps.second);
+  }
+  const int64_t G = (flat.numel() + 31) / 32;
+  auto ok = [&](const Tensor& t, int64_t need) {
+    return t.dim() == 1 && t.is_contiguous() &&
+           t.scalar_type() == at::kByte && t.numel() >= need &&
+           t.device() == flat.device();
+  };
+  TORCH_CHECK(ok(*payload_out, G * 16) && ok(*scales_out, G),
+              "debug_mx4_quantize: payload_out and scales_out must be flat "
+              "contiguous uint8 tensors with at least G*16 and G elements");
+  auto ps = mx4_quantize(flat, payload_out->narrow(0, 0, G * 16),
+                         scales_out->narrow(0, 0, G));
+  return std::make_tuple(ps.first, ps.second);
+}
+
+Tensor debug_mx4_dequantize_blocks(const Tensor& payload,
+                                   const Tensor& scales, int64_t P,
+                                   int64_t rows, int64_t row_elems,
+                                   at::ScalarType dtype,
+                                   const c10::optional<Tensor>& out) {
+  TORCH_CHECK(payload.scalar_type() == at::kByte &&
+                  scales.scalar_type() == at::kByte && P >= 1 && P <= 65535 &&
+                  rows >= 1 && row_elems >= 1 &&
+                  scales.numel() == P * ((rows * row_elems + 31) / 32) &&
+                  payload.numel() == scales.numel() * 16,
+              "debug_mx4_dequantize_blocks expects uint8 payload [P, Gb*16] "
+              "and scales [P, Gb], Gb = ceil(rows*row_elems/32), 1..65535 "
+              "blocks");
+  auto pin = payload.contiguous().view({-1});
+  auto sin = scales.contiguous().view({-1});
+  if (!out.has_value()) {
+    return mx4_dequantize_blocks(pin, sin, (int)P, rows, row_elems, dtype);
+  }
+  const int64_t total = rows * P * row_elems;
+  check_canary_out("debug_mx4_dequantize_blocks", *out, total, dtype,
+                   pin.device(), "rows*P*row_elems");
+  return mx4_dequantize_blocks(
+      pin, sin, (int)P, rows, row_elems, dtype,
+      out->narrow(0, 0, total).view({rows, P, row_elems}));
 }
 
 std::tuple<Tensor, Tensor> debug_mx8_quantize_blocks(

@@ -78,6 +78,10 @@ struct Communicator : torch::CustomClassHolder {
   // float32/bfloat16/float16 only. Backward: ReducescatterCompressed of the
   // gradient. A world of one returns an exact clone.
   at::Tensor AllgatherCompressed(const at::Tensor& input, int64_t axis);
+  // The same op over the mxfp4 wire (e2m1 nibbles, 17/32 byte per element):
+  // what AllgatherCompressed(..., wire="mxfp4") calls. Semantics, checks and
+  // the backward (ReducescatterCompressed on the mxfp8 wire) are unchanged.
+  at::Tensor AllgatherCompressedFp4(const at::Tensor& input, int64_t axis);
   // Equal-count, two-axis all-to-all over the mxfp8 wire (MI355X
   // extension): the scatter axis is split into GetSize() equal blocks, a
   // fused gfx950 kernel quantizes every block in place (groups of 32 that
@@ -270,6 +274,18 @@ at::Tensor debug_mx8_reduce_to(const at::Tensor& payload,
 at::Tensor debug_mx8_dequantize_blocks(const at::Tensor& payload,
                                        const at::Tensor& scales, int64_t rows,
                                        int64_t row_elems,
+                                       at::ScalarType dtype,
+                                       const c10::optional<at::Tensor>& out);
+// mxfp4: x (any shape, flattened) -> (payload [G*16], scales [G]); with the
+// two outs (flat uint8, at least that long) the bytes are written in place.
+std::tuple<at::Tensor, at::Tensor> debug_mx4_quantize(
+    const at::Tensor& x, const c10::optional<at::Tensor>& payload_out,
+    const c10::optional<at::Tensor>& scales_out);
+// mxfp4 allgather tail: payload P*Gb*16 bytes, scales P*Gb bytes,
+// Gb = ceil(rows*row_elems/32) -> [rows, P, row_elems] of dtype
+at::Tensor debug_mx4_dequantize_blocks(const at::Tensor& payload,
+                                       const at::Tensor& scales, int64_t P,
+                                       int64_t rows, int64_t row_elems,
                                        at::ScalarType dtype,
                                        const c10::optional<at::Tensor>& out);
 // flat contiguous x of rows*nblocks*row_elems elements seen as

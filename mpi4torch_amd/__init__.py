@@ -254,10 +254,11 @@ class MPI_Communicator:
             return self._comm.ReducescatterCompressed(tensor, axis)
         return self._comm.ReducescatterCompressedStochastic(tensor, axis, seed)
 
-    def AllgatherCompressed(self, tensor: torch.Tensor,
-                            axis: int = 0) -> torch.Tensor:
-        """Allgather that travels as block-scaled fp8 (MI355X extension):
-        the FSDP parameter primitive over the mxfp8 wire.
+    def AllgatherCompressed(self, tensor: torch.Tensor, axis: int = 0,
+                            wire: str = "mxfp8") -> torch.Tensor:
+        """Allgather that travels as block-scaled fp8 or fp4 (MI355X
+        extension): the FSDP parameter primitive over the mxfp8 wire, or
+        with ``wire="mxfp4"`` over the mxfp4 wire.
 
         Every rank's tensor (float32, bfloat16 or float16) must have the
         same size on ``axis`` (Allgather handles variable counts); the
@@ -277,8 +278,22 @@ class MPI_Communicator:
         Backward: ReducescatterCompressed of the gradient along ``axis`` —
         the exact adjoint of the concatenation; quantization is
         straight-through and the gradient itself travels compressed.
+
+        ``wire="mxfp4"`` replaces the e4m3 payload byte by an OCP e2m1
+        nibble (values 0, 0.5, 1, 1.5, 2, 3, 4, 6 times the group's power
+        of two): 17/32 byte per element, 0.515 of the mxfp8 wire, at about
+        one significant bit less than two. Everything else is the same op,
+        and the backward still travels as mxfp8. It suits values that are
+        re-sent from a full-precision master copy, such as FSDP parameters;
+        the codec rule is in doc/kernels.md.
         """
-        return self._comm.AllgatherCompressed(tensor, axis)
+        if wire == "mxfp8":
+            return self._comm.AllgatherCompressed(tensor, axis)
+        if wire == "mxfp4":
+            return self._comm.AllgatherCompressedFp4(tensor, axis)
+        raise ValueError(
+            "mpi4torch_amd: AllgatherCompressed: wire must be 'mxfp8' or "
+            "'mxfp4', got '" + wire + "'")
 
     def AlltoallCompressed(self, tensor: torch.Tensor, gatheraxis: int,
                            scatteraxis: int) -> torch.Tensor:

@@ -22,8 +22,11 @@ Usage::
 Compression (world > 1 only; a world of one runs no collective and
 compresses nothing): ``param_compression="mxfp8"`` gathers every unit's
 parameters with AllgatherCompressed (block-scaled fp8 wire, 33/32 byte per
-element). The master shard keeps full precision; every rank, the owner
-included, computes with the same dequantized parameters. That op is blocking
+element); ``param_compression="mxfp4"`` does so on the op's fp4 wire (e2m1
+nibbles, 17/32 byte per element), which costs the optimizer nothing because
+the master shard never travels. The master shard keeps full precision; every
+rank, the owner included, computes with the same dequantized parameters. That
+op is blocking
 (stream-ordered on GPU, host-blocking on gloo) and has no non-blocking
 variant, so nothing is prefetched for such a model: the gather happens in
 materialize(). ``grad_compression="mxfp8"`` reduces every unit's gradient
@@ -135,7 +138,8 @@ class _Unit:
             local = local.to(self.flat.dtype)  # model dtype on the wire
         if self.comm.size > 1:
             # compressed: every rank, the owner included, gets dq(q(shard))
-            full = (self.comm.AllgatherCompressed(local, 0)
+            full = (self.comm.AllgatherCompressed(
+                        local, 0, wire=self.param_compression)
                     if self.param_compression is not None
                     else self.comm.Allgather(local, 0))
             self.flat.copy_(full)
@@ -188,10 +192,10 @@ class FullyShardedDataParallel(torch.nn.Module):
                  grad_compression: Optional[str] = None,
                  compression_seed: int = 0):
         super().__init__()
-        if param_compression not in (None, "mxfp8"):
+        if param_compression not in (None, "mxfp8", "mxfp4"):
             raise ValueError(
-                "mpi4torch_amd FSDP: param_compression must be None or "
-                f"'mxfp8', got {param_compression!r}")
+                "mpi4torch_amd FSDP: param_compression must be None, 'mxfp8' "
+                f"or 'mxfp4', got {param_compression!r}")
         if grad_compression not in (None, "mxfp8", "mxfp8-sr"):
             raise ValueError(
                 "mpi4torch_amd FSDP: grad_compression must be None, 'mxfp8' "

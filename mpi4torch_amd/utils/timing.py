@@ -52,6 +52,13 @@ def mxfp8_allgather_wire_bytes(numel: int, world: int) -> int:
     return (world - 1) * 33 * ((numel + 31) // 32)
 
 
+def mxfp4_allgather_wire_bytes(numel: int, world: int) -> int:
+    """mxfp8_allgather_wire_bytes for ``AllgatherCompressed(wire="mxfp4")``:
+    16 payload bytes of e2m1 nibbles plus the scale byte per group of 32,
+    17/32 byte per element."""
+    return (world - 1) * 17 * ((numel + 31) // 32)
+
+
 def alltoall_compressed_wire_bytes(numel: int, world: int) -> int:
     """Bytes one rank sends in AlltoallCompressed of its own tensor of
     ``numel`` elements over ``world`` ranks: every other rank's block of

@@ -134,10 +134,10 @@ class TracedCommunicator:
             "ReducescatterCompressed", tensor,
             lambda: self._comm.ReducescatterCompressed(tensor, axis, seed))
 
-    def AllgatherCompressed(self, tensor, axis=0):
+    def AllgatherCompressed(self, tensor, axis=0, wire="mxfp8"):
         return self._record(
             "AllgatherCompressed", tensor,
-            lambda: self._comm.AllgatherCompressed(tensor, axis))
+            lambda: self._comm.AllgatherCompressed(tensor, axis, wire))
 
     def AlltoallCompressed(self, tensor, gatheraxis, scatteraxis):
         return self._record(

@@ -13,6 +13,7 @@ reported GB/s counts actual bytes touched. Run on an MI355X box:
     python tools/kernel_microbench.py --mx8-combine             # only that part
     python tools/kernel_microbench.py --mx8-weighted            # only that part
     python tools/kernel_microbench.py --mx8-sr    # stochastic rounding vs nearest
+    python tools/kernel_microbench.py --mx4       # mxfp4 kernels vs mxfp8 siblings
 
 The mxfp8 section times the three codec kernels and, in the same run and
 alternating with it, the sibling fp8_reduce kernel at the same P and n, so
@@ -691,6 +692,65 @@ def mx8_sr_section(repeats=5):
            lambda: C._mx8_reduce_sr(pay, sc, 1, 1, 0, 0),
            (P + 1) * (33 * N // 32))
 
+
+def mx4_section(repeats=5):
+    """The mxfp4 kernels against their mxfp8 siblings at equal N, alternating
+    in the same run: quantize at 256Mi elements, dequantize_blocks at P = 8
+    blocks of 32Mi elements as (a) one row, (b) rows of 40 chunks of 8
+    elements, (c) one odd row (the general twins). Bytes are what each kernel
+    moves: N*esize on the tensor side plus 17N/32 (mx4) or 33N/32 (mx8)."""
+    C = m._C
+    med = lambda v: sorted(v)[len(v) // 2]
+
+    def versus(tag, mx8, mx4, tensor_bytes, n):
+        t8, t4 = [], []
+        for _ in range(repeats):
+            t8.append(timeit(mx8))
+            t4.append(timeit(mx4))
+        for name, t, wire in (("mx8_" + tag, t8, 33), ("mx4_" + tag, t4, 17)):
+            nbytes = tensor_bytes + wire * n // 32
+            print(f"{name:40s} {med(t)*1e3:9.1f} us  "
+                  f"{nbytes/med(t)/1e6:8.1f} GB/s  (min {min(t)*1e3:.1f} max "
+                  f"{max(t)*1e3:.1f} us, {repeats} repeats)", flush=True)
+        print(f"  mx4 / mx8 time ratio {med(t4)/med(t8):.3f}, mx8 spread "
+              f"{min(t8)/med(t8):.3f}-{max(t8)/med(t8):.3f}", flush=True)
+
+    NQ = 256 << 20
+    for dtype, tag in ((torch.float32, "fp32"), (torch.bfloat16, "bf16")):
+        x = torch.randn(NQ, device="cuda")
+        x.view(-1, 32).mul_(torch.rand(NQ // 32, 1, device="cuda"))
+        x = x.to(dtype)
+        versus(f"quantize {tag} N={NQ>>20}Mi", lambda: C._mx8_quantize(x),
+               lambda: C._mx4_quantize(x), NQ * x.element_size(), NQ)
+        del x
+    Lb = 32 << 20
+    for rows, row_elems, what in ((1, Lb, "a: one row"),
+                                  (Lb // 320, 320, "b: rows of 40 chunks"),
+                                  (1, Lb + 1, "c: odd row, twins")):
+        L = rows * row_elems
+        Gb = (L + 31) // 32
+        sc = torch.randint(120, 135, (P, Gb), dtype=torch.uint8, device="cuda")
+        pay8 = torch.randint(0, 0x7e, (P, Gb * 32), dtype=torch.uint8,
+                             device="cuda")
+        pay4 = torch.randint(0, 256, (P, Gb * 16), dtype=torch.uint8,
+                             device="cuda")
+        for dtype, tag in ((torch.float32, "fp32"), (torch.bfloat16, "bf16")):
+            es = torch.empty((), dtype=dtype).element_size()
+            out = torch.empty(rows * P * row_elems, dtype=dtype, device="cuda")
+            versus(f"dequantize_blocks {tag} ({what})",
+                   lambda: C._mx8_dequantize_blocks(pay8, sc, rows, row_elems,
+                                                    dtype, out=out),
+                   lambda: C._mx4_dequantize_blocks(pay4, sc, P, rows,
+                                                    row_elems, dtype, out=out),
+                   P * L * es, P * Gb * 32)
+            del out
+        del sc, pay8, pay4
+
+
+if "--mx4" in sys.argv:
+    mx4_section()
+    dist.destroy_process_group()
+    sys.exit(0)
 
 if "--mx8-sr" in sys.argv:
     mx8_sr_section()
