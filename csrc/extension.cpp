@@ -58,6 +58,7 @@ static auto communicator_class =
              &Communicator::ReducescatterCompressedStochastic)
         .def("AllgatherCompressed", &Communicator::AllgatherCompressed)
         .def("AllgatherCompressedFp4", &Communicator::AllgatherCompressedFp4)
+        .def("AllgatherCompressedFp6", &Communicator::AllgatherCompressedFp6)
         .def("AlltoallCompressed", &Communicator::AlltoallCompressed)
         .def("Scatter", &Communicator::Scatter)
         .def("Alltoall", &Communicator::Alltoall)
@@ -145,6 +146,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("payload_out") = c10::optional<at::Tensor>(),
         py::arg("scales_out") = c10::optional<at::Tensor>());
   m.def("_mx4_dequantize_blocks", &m4a::debug_mx4_dequantize_blocks,
+        py::arg("payload"), py::arg("scales"), py::arg("P"), py::arg("rows"),
+        py::arg("row_elems"), py::arg("dtype"),
+        py::arg("out") = c10::optional<at::Tensor>());
+  m.def("_mx6_quantize", &m4a::debug_mx6_quantize, py::arg("x"),
+        py::arg("payload_out") = c10::optional<at::Tensor>(),
+        py::arg("scales_out") = c10::optional<at::Tensor>());
+  m.def("_mx6_dequantize_blocks", &m4a::debug_mx6_dequantize_blocks,
         py::arg("payload"), py::arg("scales"), py::arg("P"), py::arg("rows"),
         py::arg("row_elems"), py::arg("dtype"),
         py::arg("out") = c10::optional<at::Tensor>());

@@ -195,6 +195,24 @@ void launch_mx4_dequantize_blocks(const void* payload, const void* scales,
                                   int64_t row_elems, int dtype,
                                   hipStream_t stream);
 
+// mxfp6 codec, the third wire of AllgatherCompressed (csrc/mx8_kernels.hip):
+// groups of 32 consecutive elements -> 24 payload bytes of OCP e2m3 codes
+// (a little-endian bit stream, code i in bits 6i..6i+5 of the group) + one
+// E8M0 scale byte (255 = non-finite group), 25/32 byte per element. The rule
+// is defined by the torch composite in csrc/ops.cpp (mx6_quantize_groups);
+// the kernels match it byte for byte. dtype codes as above.
+//
+// Quantize n_elems elements: payload gets ceil(n/32)*24 bytes (the partial
+// last group is zero-padded), scales ceil(n/32) bytes.
+void launch_mx6_quantize(const void* in, void* payload, void* scales,
+                         int64_t n_elems, int dtype, hipStream_t stream);
+// launch_mx4_dequantize_blocks on the mxfp6 wire: payload [nblocks][Gb*24],
+// scales [nblocks][Gb]; the output and its bounds are the same.
+void launch_mx6_dequantize_blocks(const void* payload, const void* scales,
+                                  void* out, int nblocks, int64_t rows,
+                                  int64_t row_elems, int dtype,
+                                  hipStream_t stream);
+
 // One segment of the variable-count codec kernels below: `count` slices of
 // the stream side starting at slice `displ`, whose mxfp8 stream starts at
 // group `goff` (payload byte 32*goff, scale byte goff).

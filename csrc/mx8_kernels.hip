@@ -75,7 +75,8 @@
 //   SegCursor  : the (b, c, a) walk of the two segments twins.
 // The mxfp4 wire of AllgatherCompressed (e2m1 nibbles under the same groups
 // and scale byte) has its quantize and dequantize_blocks kernels at the end
-// of this file, with its rule.
+// of this file, with its rule; the mxfp6 wire (e2m3 codes, 24 payload bytes
+// per group) follows it.
 // On the host, by_dtype / by_width / by_width_mode turn the run-time dtype,
 // index width and segment mode into template arguments, grid2d is the capped
 // 2-D grid, and launch_segments_t is both segments launchers.
@@ -2538,6 +2539,366 @@ void launch_mx4_dequantize_blocks(const void* payload, const void* scales,
   if (nblocks <= 0 || rows <= 0 || row_elems <= 0) return;
   by_dtype(dtype, [&](auto k) {
     launch_mx4_dequantize_blocks_t<k>(static_cast<const u8*>(payload),
+                                      static_cast<const u8*>(scales), out,
+                                      nblocks, rows, row_elems, stream);
+  });
+}
+
+// ===========================================================================
+// mxfp6 (e2m3): the third wire of AllgatherCompressed
+// ===========================================================================
+//
+// The family's rule with OCP e2m3 in place of e4m3 (normative in csrc/ops.cpp,
+// mx6_quantize_groups / mx6_dequantize_groups): a group of 32 elements is 24
+// payload bytes plus the E8M0 scale byte, 25/32 byte per element. A code is
+// sign<<5 | e<<3 | m with bias 1: m/8 for e = 0, (1 + m/8) * 2^(e-1) above,
+// maximum 7.5. The 32 codes are a little-endian bit stream: code i sits in
+// bits 6i..6i+5 of the group's 192. With amax = m*2^k, m in [0.5,1): E = k-3
+// if m <= 0.9375 else k-2, clamped to [-127,127], so amax*2^-E <= 7.5 and the
+// conversion cannot saturate.
+//
+// The gfx950 packed fp6 converts work on 32 values per lane and their
+// element order, ties and signed zeros are not established, so they are not
+// used. The conversions go through what the mxfp8 kernels already rely on:
+//   encode : e2m3 is e4m3 with its exponent range cut to the lowest four
+//            fields: both have three mantissa bits and subnormals below their
+//            first normal binade, 2^0 here and 2^-6 there. So the e4m3 byte
+//            of y * 2^-6 (the hardware RNE convert of quant4, under the
+//            exponent E + 6) has the e2m3 magnitude in its low five bits and
+//            the sign in bit 7; |y| <= 7.5 keeps its exponent field <= 3.
+//            Four bytes become four codes in three mask operations, and 24
+//            contiguous bits in seven more.
+//   decode : the 5-bit magnitude shifted to fp32 bits 20..24 is the value
+//            times 2^-126, fp32 subnormals included (e = 0 is a subnormal
+//            there too); one ldexpf applies 2^126 and the shared exponent.
+//
+// Three kernels and the twins of the first and last, all 256 threads,
+// grid-stride, no LDS:
+//   quantize  : 16 elements per lane, 2 lanes per group, for every dtype (two
+//               16-byte loads for the 16-bit dtypes, four for fp32); the amax
+//               crosses the pair by one xor-shuffle; a lane's 16 codes are 96
+//               bits, three dwords stored at once, a wave 768 contiguous
+//               bytes; the wave's 32 scale bytes leave through
+//               store_scales<2>. The loop covers ALL G*2 lane slots: elements
+//               past N are zeros and store the zero padding.
+//   dequantize_blocks : the allgather tail, mx4_dequantize_blocks_kernel's
+//               geometry and its one 16-byte store per lane, fed by the 6
+//               (16-bit dtypes, 8 elements) or 3 (fp32, 4 elements) payload
+//               bytes of the chunk, read as the tail of one unaligned load.
+//   its general twin : the destination-aligned split of the other two wires;
+//               a chunk's codes start at any of four bit phases (see there).
+
+namespace {
+
+__device__ inline int mx6_scale_byte(unsigned amax_bits, int* E) {
+  if (amax_bits >= kInfBits) {
+    *E = 0;
+    return 255;
+  }
+  const int e = (int)(amax_bits >> 23);
+  const unsigned f = amax_bits & 0x7fffffu;
+  int ex;
+  if (amax_bits == 0) {
+    ex = 0;
+  } else if (e == 0) {
+    ex = -127;  // fp32 subnormal amax: k <= -126, k-2 clamps
+  } else {
+    // amax = 1.f * 2^(e-127) = m * 2^(e-126); m <= 0.9375 <=> f <= 0x700000
+    ex = (e - 126) - (f <= 0x700000u ? 3 : 2);
+    if (ex < -127) ex = -127;
+  }
+  *E = ex;
+  return ex + 127;
+}
+
+// four values under the shared exponent E -> their four codes, 24 bits
+__device__ inline unsigned mx6_quant4(float a, float b, float c, float d,
+                                      int E) {
+  const unsigned b8 = quant4(a, b, c, d, E + 6);  // e4m3 bytes of y * 2^-6
+  const unsigned c8 = (b8 & 0x1f1f1f1fu) | ((b8 >> 2) & 0x20202020u);
+  return (c8 & 0x3fu) | ((c8 >> 2) & 0xfc0u) | ((c8 >> 4) & 0x3f000u) |
+         ((c8 >> 6) & 0xfc0000u);
+}
+
+// a lane's 16 elements under the shared exponent E -> its 96 payload bits
+__device__ inline void mx6_quant16(const float (&x)[16], int E,
+                                   unsigned (&w)[3]) {
+  unsigned t[4];
+  for (int j = 0; j < 4; ++j) {
+    t[j] = mx6_quant4(x[4 * j], x[4 * j + 1], x[4 * j + 2], x[4 * j + 3], E);
+  }
+  w[0] = t[0] | t[1] << 24;
+  w[1] = t[1] >> 8 | t[2] << 16;
+  w[2] = t[2] >> 16 | t[3] << 8;
+}
+
+// one code under scale byte sb (the bits above the code are ignored)
+__device__ inline float mx6_dequant(unsigned code, int sb) {
+  const float t =
+      __uint_as_float(((code & 31u) << 20) | ((code & 32u) << 26));
+  return sb == 255 ? __uint_as_float(kQNaNBits) : ldexpf(t, sb - 1);
+}
+
+// ---- quantize -----------------------------------------------------------
+
+template <int K>
+__global__ __launch_bounds__(256) void mx6_quantize_kernel(
+    const void* __restrict__ in, u8* __restrict__ pay, u8* __restrict__ sc,
+    long long G, long long N) {
+  const long long slots = G * 2;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  const int lane = threadIdx.x & 63;
+  // wave-uniform trip count: the shuffle below and those in store_scales need
+  // every lane present; slots is even, so a group is never cut
+  for (long long i0 = (long long)blockIdx.x * blockDim.x + (threadIdx.x & ~63);
+       i0 < slots; i0 += stride) {
+    const long long i = i0 + lane;
+    const bool act = i < slots;
+    float x[16];
+    if (act) {
+      // slot i is the mx4 layout's slots 2i and 2i+1 (zeros past N)
+      mx4_load8<K>(in, 2 * i, N, *reinterpret_cast<float(*)[8]>(&x[0]));
+      mx4_load8<K>(in, 2 * i + 1, N, *reinterpret_cast<float(*)[8]>(&x[8]));
+    } else {
+      for (int k = 0; k < 16; ++k) x[k] = 0.0f;
+    }
+    unsigned a = amax_bits_of(x);
+    const unsigned o = (unsigned)__shfl_xor((int)a, 1);
+    a = o > a ? o : a;
+    int E;
+    const int sb = mx6_scale_byte(a, &E);
+    if (act) {
+      unsigned w[3];
+      mx6_quant16(x, E, w);
+      unsigned* p = reinterpret_cast<unsigned*>(pay) + 3 * i;
+      for (int d = 0; d < 3; ++d) {
+        __builtin_nontemporal_store(sb == 255 ? 0u : w[d], p + d);
+      }
+    }
+    store_scales<2>(sc, i0 / 2, G, sb, lane);
+  }
+}
+
+// One thread per group, any alignment of the input and payload bases.
+template <int K>
+__global__ __launch_bounds__(256) void mx6_quantize_kernel_scalar(
+    const void* __restrict__ in, u8* __restrict__ pay, u8* __restrict__ sc,
+    long long G, long long N) {
+  using T = typename Elem<K>::type;
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < G;
+       g += stride) {
+    const T* p = reinterpret_cast<const T*>(in) + g * 32;
+    const long long left = N - g * 32;
+    float x[32];
+    for (int k = 0; k < 32; ++k) {
+      x[k] = k < left ? elem_to_f32<K>(p[k]) : 0.0f;
+    }
+    int E;
+    const int sb = mx6_scale_byte(amax_bits_of(x), &E);
+    for (int j = 0; j < 8; ++j) {  // four codes -> three bytes
+      const unsigned t =
+          sb == 255 ? 0u
+                    : mx6_quant4(x[4 * j], x[4 * j + 1], x[4 * j + 2],
+                                 x[4 * j + 3], E);
+      for (int k = 0; k < 3; ++k) pay[g * 24 + 3 * j + k] = (u8)(t >> (8 * k));
+    }
+    sc[g] = (u8)sb;
+  }
+}
+
+// ---- dequantize_blocks (the allgather tail) ------------------------------
+//
+// pay [nblocks][Gb*24], sc [nblocks][Gb], Gb = ceil(L/32), L = rows*row_elems
+// -> out [rows][nblocks][row_elems]. Vector body: one 16-byte store per lane,
+// EPL = 8 elements for the 16-bit dtypes and 4 for fp32, as on the other two
+// wires: a lane slot of 16 elements (one 12-byte load, two or four stores at
+// a stride of 32 or 64 bytes) measured 1.2 (bf16) and 3.5 to 4.1 (fp32) times
+// the mxfp8 sibling's time (doc/kernels.md section 5). Chunk i of the block
+// is payload bytes [WB*i, WB*i + WB), WB = 6 or 3, which is no power of two:
+// the lane reads the 8 or 4 bytes that END with the chunk's last byte (one
+// unaligned load, shifted right by the 2 or 1 bytes in front; chunk 0 starts
+// at the block's first byte instead), so nothing past the payload is read.
+// It requires row_elems % EPL == 0 and a 16-byte aligned output; scale byte
+// i*EPL/32 (the group runs over the block-flat index and may straddle rows).
+// L % EPL == 0, so the partial last group is whole chunks and nothing past
+// element L is written.
+template <int K, typename I>
+__global__ __launch_bounds__(256) void mx6_dequantize_blocks_kernel(
+    const u8* __restrict__ pay, const u8* __restrict__ sc,
+    void* __restrict__ out, long long Gb, I chunks, I cpr,
+    long long nblocks) {
+  using W = std::conditional_t<K == kF32, unsigned, unsigned long long>;
+  constexpr int EPL = kMx4EPL<K>;
+  constexpr int WB = 6 * EPL / 8;            // payload bytes per chunk
+  constexpr int BACK = (int)sizeof(W) - WB;  // bytes in front of them
+  const long long r = blockIdx.y;
+  const u8* __restrict__ bp = pay + r * Gb * 24;
+  const u8* __restrict__ bs = sc + r * Gb;
+  const BlockMap<I> map{r, nblocks, cpr};
+  const I stride = (I)gridDim.x * blockDim.x;
+  for (I i = (I)blockIdx.x * blockDim.x + threadIdx.x; i < chunks;
+       i += stride) {
+    const int sb = bs[i / (32 / EPL)];
+    const int back = i ? BACK : 0;
+    W win;
+    __builtin_memcpy(&win, bp + (long long)i * WB - back, sizeof(W));
+    win >>= 8 * back;
+    float x[EPL];
+    for (int k = 0; k < EPL; ++k) {
+      x[k] = mx6_dequant((unsigned)(win >> (6 * k)), sb);
+    }
+    __builtin_nontemporal_store(pack16<K, EPL>(x),
+                                reinterpret_cast<v4u*>(out) + map(i));
+  }
+}
+
+// General twin: any row length, any alignment of the payload and output
+// bases. The split and the lane slots are those of
+// mx4_dequantize_blocks_kernel_shifted: per (block, row) segment up to EPL-1
+// head elements, whole aligned 16-byte chunks of EPL elements (8 for the
+// 16-bit dtypes, 4 for fp32), up to EPL-1 tail elements; row_elems/EPL + 2
+// slots per row. A chunk's first element src may be any element of the block,
+// so its codes start at bit 6*src: byte 6*src/8, bit phase 6*src mod 8, one
+// of 0, 6, 4, 2. The window is the ceil((phase + 6*EPL)/8) bytes from there
+// on (6 or 7 for EPL = 8, 3 or 4 for EPL = 4), read in unaligned pieces that
+// end with the chunk's last code, never past the payload, and shifted right
+// by the phase. The chunk may belong to two groups, hence two scale bytes.
+template <int K, typename I>
+__global__ __launch_bounds__(256) void mx6_dequantize_blocks_kernel_shifted(
+    const u8* __restrict__ pay, const u8* __restrict__ sc,
+    void* __restrict__ out, long long Gb, long long row_elems, I slots,
+    I total, long long nblocks) {
+  using T = typename Elem<K>::type;
+  using W = std::conditional_t<K == kF32, unsigned short, unsigned>;
+  constexpr int EPL = K == kF32 ? 4 : 8;
+  constexpr int WB = (int)sizeof(W);  // 2 or 4: the window's first piece
+  const long long r = blockIdx.y;
+  const u8* __restrict__ bp = pay + r * Gb * 24;
+  const u8* __restrict__ bs = sc + r * Gb;
+  auto code_at = [&](long long e) {
+    const long long bit = 6 * e;
+    const int ph = (int)(bit & 7);
+    unsigned v = bp[bit >> 3] >> ph;
+    if (ph > 2) v |= (unsigned)bp[(bit >> 3) + 1] << (8 - ph);
+    return v;
+  };
+  const I stride = (I)gridDim.x * blockDim.x;
+  for (I i = (I)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += stride) {
+    const I b = i / slots;
+    const long long k = (long long)(i - b * slots);
+    T* d = reinterpret_cast<T*>(out) +
+           ((long long)b * nblocks + r) * row_elems;  // the segment
+    const long long s0 = (long long)b * row_elems;    // its block-flat start
+    long long head =
+        (long long)(((16 - (reinterpret_cast<uintptr_t>(d) & 15)) & 15) /
+                    sizeof(T));
+    if (head > row_elems) head = row_elems;
+    const long long nchunks = (row_elems - head) / EPL;
+    if (k < nchunks) {
+      const long long e = head + k * EPL;
+      const long long src = s0 + e;
+      const int ph = (int)((6 * src) & 7);
+      const u8* p = bp + ((6 * src) >> 3);
+      // bytes [0, WB), [WB, WB + WB/2) and, off phase 0, one more
+      W a;
+      __builtin_memcpy(&a, p, WB);
+      unsigned long long win = a;
+      if constexpr (EPL == 8) {
+        unsigned short m;
+        __builtin_memcpy(&m, p + 4, 2);
+        win |= (unsigned long long)m << 32;
+      } else {
+        win |= (unsigned long long)p[2] << 16;
+      }
+      if (ph) win |= (unsigned long long)p[WB + WB / 2] << (12 * WB);
+      win >>= ph;
+      const long long g0 = src >> 5;
+      const int sb0 = bs[g0];
+      const int sb1 = bs[(src + EPL - 1) >> 5];
+      float x[EPL];
+      for (int t = 0; t < EPL; ++t) {
+        x[t] = mx6_dequant((unsigned)(win >> (6 * t)),
+                           ((src + t) >> 5) == g0 ? sb0 : sb1);
+      }
+      __builtin_nontemporal_store(pack16<K, EPL>(x),
+                                  reinterpret_cast<v4u*>(d + e));
+    } else if (k >= (long long)slots - 2) {
+      // head [0, head) or tail [head + nchunks*EPL, row_elems): fewer than
+      // EPL elements each, stored one by one
+      const bool is_head = k == (long long)slots - 2;
+      const long long lo = is_head ? 0 : head + nchunks * EPL;
+      const long long hi = is_head ? head : row_elems;
+      for (long long e = lo; e < hi; ++e) {
+        d[e] = f32_to_elem<K>(mx6_dequant(code_at(s0 + e), bs[(s0 + e) >> 5]));
+      }
+    }
+  }
+}
+
+template <int K>
+void launch_mx6_quantize_t(const void* in, u8* pay, u8* sc, int64_t N,
+                           hipStream_t stream) {
+  const long long G = (N + 31) / 32;
+  if (aligned(in, 16) && aligned(pay, 4)) {
+    hipLaunchKernelGGL((mx6_quantize_kernel<K>), dim3(grid_for(G * 2)),
+                       dim3(256), 0, stream, in, pay, sc, G, (long long)N);
+  } else {
+    hipLaunchKernelGGL((mx6_quantize_kernel_scalar<K>), dim3(grid_for(G)),
+                       dim3(256), 0, stream, in, pay, sc, G, (long long)N);
+  }
+}
+
+template <int K>
+void launch_mx6_dequantize_blocks_t(const u8* pay, const u8* sc, void* out,
+                                    int nblocks, int64_t rows,
+                                    int64_t row_elems, hipStream_t stream) {
+  const long long L = rows * row_elems;
+  const long long Gb = (L + 31) / 32;
+  // row_elems % EPL == 0 with an aligned out keeps every chunk's destination
+  // aligned; the payload is read by unaligned loads in either kernel.
+  constexpr int EPL = kMx4EPL<K>;
+  if (aligned(out, 16) && row_elems % EPL == 0) {
+    const long long chunks = L / EPL;
+    const long long cpr = row_elems / EPL;
+    by_width(chunks, [&](auto i) {
+      using I = decltype(i);
+      hipLaunchKernelGGL((mx6_dequantize_blocks_kernel<K, I>),
+                         grid2d(chunks, nblocks), dim3(256), 0, stream, pay,
+                         sc, out, Gb, (I)chunks, (I)cpr, (long long)nblocks);
+    });
+  } else {
+    const long long slots = row_elems / EPL + 2;
+    const long long total = rows * slots;
+    by_width(total, [&](auto i) {
+      using I = decltype(i);
+      hipLaunchKernelGGL((mx6_dequantize_blocks_kernel_shifted<K, I>),
+                         grid2d(total, nblocks), dim3(256), 0, stream, pay, sc,
+                         out, Gb, (long long)row_elems, (I)slots, (I)total,
+                         (long long)nblocks);
+    });
+  }
+}
+
+} // namespace
+
+void launch_mx6_quantize(const void* in, void* payload, void* scales,
+                         int64_t n_elems, int dtype, hipStream_t stream) {
+  if (n_elems <= 0) return;
+  by_dtype(dtype, [&](auto k) {
+    launch_mx6_quantize_t<k>(in, static_cast<u8*>(payload),
+                             static_cast<u8*>(scales), n_elems, stream);
+  });
+}
+
+void launch_mx6_dequantize_blocks(const void* payload, const void* scales,
+                                  void* out, int nblocks, int64_t rows,
+                                  int64_t row_elems, int dtype,
+                                  hipStream_t stream) {
+  if (nblocks <= 0 || rows <= 0 || row_elems <= 0) return;
+  by_dtype(dtype, [&](auto k) {
+    launch_mx6_dequantize_blocks_t<k>(static_cast<const u8*>(payload),
                                       static_cast<const u8*>(scales), out,
                                       nblocks, rows, row_elems, stream);
   });

@@ -1360,6 +1360,162 @@ Tensor mx4_allgather(Transport& tr, const Tensor& in, int64_t rows,
                                in.scalar_type());
 }
 
+// ------------------------- mxfp6 compressed allgather ----------------------
+//
+// The family's codec with OCP e2m3 in place of e4m3 (normative; the gfx950
+// kernels match this torch composite byte for byte): groups of 32 consecutive
+// elements of the flat tensor, each 24 payload bytes + one E8M0 scale byte.
+// A code is sign<<5 | e<<3 | m, exponent bias 1, no infinity and no NaN:
+// e = 0 is m/8, e = 1..3 is (1 + m/8) * 2^(e-1), maximum 7.5. The group's 32
+// codes are a little-endian bit stream, code i in bits 6i..6i+5 of its 192
+// bits (bit 0 the LSB of byte 0); four codes fill three bytes:
+//   b0 = c0 | (c1&3)<<6,  b1 = c1>>2 | (c2&15)<<4,  b2 = c2>>4 | c3<<2.
+//   quantize : amax over |x| in fp32. Non-finite group -> scale 255, zero
+//              payload. amax == 0 -> E = 0. Else amax = m*2^k (frexp,
+//              m in [0.5,1)): E = k-3 if m <= 0.9375 else k-2, clamped to
+//              [-127,127] — the smallest E with amax*2^-E <= 7.5. Scale byte
+//              E+127; code = RNE(x * 2^-E) onto the grid, ties to the even
+//              code (never saturates); the sign bit is kept, also where the
+//              value rounds to zero.
+//   dequant  : value(code) * 2^E with sign (exact); scale 255 -> NaN group.
+
+// the value of magnitude code c = 0..31
+float mx6_grid_value(int c) {
+  const int e = c >> 3, m = c & 7;
+  return e == 0 ? m / 8.0f : std::ldexp(1.0f + m / 8.0f, e - 1);
+}
+
+// |y| <= 7.5 -> code 0..31: the count of the grid's 31 rounding boundaries
+// that |y| passes. A tie goes up exactly where the upper code is even.
+Tensor mx6_codes(const Tensor& ay) {
+  auto c = at::zeros_like(ay, ay.options().dtype(at::kByte));
+  for (int u = 1; u < 32; ++u) {
+    const float mid = 0.5f * (mx6_grid_value(u - 1) + mx6_grid_value(u));
+    c += (u % 2 == 0 ? ay.ge(mid) : ay.gt(mid)).to(at::kByte);
+  }
+  return c;
+}
+
+// xg: [G, 32] fp32 -> (payload [G, 24] u8, scales [G] u8)
+std::pair<Tensor, Tensor> mx6_quantize_groups(const Tensor& xg) {
+  auto finite = at::isfinite(xg).all(1);
+  auto amax = xg.abs().amax(1).masked_fill(finite.logical_not(), 0);
+  auto mk = at::frexp(amax);
+  auto m = std::get<0>(mk);
+  auto k = std::get<1>(mk).to(at::kInt);
+  auto E =
+      k - at::where(m.le(0.9375), at::full_like(k, 3), at::full_like(k, 2));
+  E = at::where(amax.eq(0), at::zeros_like(E), E).clamp(-127, 127);
+  auto scaled = xg * mx8_pow2(-E).unsqueeze(1);
+  auto c = mx6_codes(scaled.abs()) + at::signbit(scaled).to(at::kByte) * 32;
+  c = at::where(finite.unsqueeze(1), c, at::zeros_like(c)).view({-1, 8, 4});
+  auto c0 = c.select(2, 0), c1 = c.select(2, 1), c2 = c.select(2, 2),
+       c3 = c.select(2, 3);
+  auto pay = at::stack({c0 + c1.bitwise_and(3) * 64,
+                        c1.bitwise_right_shift(2) + c2.bitwise_and(15) * 16,
+                        c2.bitwise_right_shift(4) + c3 * 4},
+                       2)
+                 .view({-1, 24});
+  auto sc = at::where(finite, E + 127, at::full_like(E, 255)).to(at::kByte);
+  return {pay.contiguous(), sc.contiguous()};
+}
+
+// payload [G, 24] u8, scales [G] u8 -> [G, 32] fp32
+Tensor mx6_dequantize_groups(const Tensor& pay, const Tensor& sc) {
+  auto b = pay.view({-1, 8, 3});
+  auto b0 = b.select(2, 0), b1 = b.select(2, 1), b2 = b.select(2, 2);
+  auto c = at::stack({b0.bitwise_and(63),
+                      b0.bitwise_right_shift(6) + b1.bitwise_and(15) * 4,
+                      b1.bitwise_right_shift(4) + b2.bitwise_and(3) * 16,
+                      b2.bitwise_right_shift(2)},
+                     2)
+               .view({-1, 32});
+  std::vector<float> values(32);
+  for (int u = 0; u < 32; ++u) values[u] = mx6_grid_value(u);
+  auto grid = at::tensor(values, pay.options().dtype(at::kFloat));
+  auto v = grid.index({c.bitwise_and(31).to(at::kLong)});
+  v = at::where(c.bitwise_and(32).ne(0), v.neg(), v);
+  auto E = (sc.to(at::kInt) - 127).clamp(-127, 127);
+  auto d = v * mx8_pow2(E).unsqueeze(1);
+  return at::where(sc.eq(255).unsqueeze(1),
+                   at::full_like(d, std::numeric_limits<float>::quiet_NaN()),
+                   d);
+}
+
+// flat contiguous x -> (payload [G*24] u8, scales [G] u8), G = ceil(N/32)
+std::pair<Tensor, Tensor> mx6_quantize(
+    const Tensor& x, const c10::optional<Tensor>& payload_out = c10::nullopt,
+    const c10::optional<Tensor>& scales_out = c10::nullopt) {
+  const int dt = mx8_dtype_code(x.scalar_type(), "mxfp6 compression");
+  const int64_t N = x.numel();
+  const int64_t G = (N + 31) / 32;
+  auto bopts = x.options().dtype(at::kByte);
+  auto pay = out_or_empty(payload_out, {G * 24}, bopts);
+  auto sc = out_or_empty(scales_out, {G}, bopts);
+  if (x.is_cuda()) {
+    launch_mx6_quantize(x.data_ptr(), pay.data_ptr(), sc.data_ptr(), N, dt,
+                        current_gpu_stream(x));
+    return {pay, sc};
+  }
+  auto padded = at::zeros({G * 32}, x.options().dtype(at::kFloat));
+  padded.narrow(0, 0, N).copy_(x.view({-1}));
+  auto ps = mx6_quantize_groups(padded.view({G, 32}));
+  if (!payload_out.has_value()) return {ps.first.view({-1}), ps.second};
+  pay.copy_(ps.first.view({-1}));
+  sc.copy_(ps.second);
+  return {pay, sc};
+}
+
+// mx4_dequantize_blocks on the mxfp6 wire: pay [P * Gb*24], sc [P * Gb] ->
+// [rows, P, row_elems] of `dtype`,
+//   out[b, r, j] = dq(block r)[b*row_elems + j].to(dtype)
+Tensor mx6_dequantize_blocks(const Tensor& pay, const Tensor& sc, int P,
+                             int64_t rows, int64_t row_elems,
+                             at::ScalarType dtype,
+                             const c10::optional<Tensor>& out_opt =
+                                 c10::nullopt) {
+  const int dt = mx8_dtype_code(dtype, "mxfp6 compression");
+  TORCH_CHECK(P >= 1 && P <= 65535,
+              "mpi4torch_amd: mx6_dequantize_blocks supports 1..65535 "
+              "blocks, got ", P);
+  auto out = out_or_empty(out_opt, {rows, (int64_t)P, row_elems},
+                          pay.options().dtype(dtype));
+  if (out.numel() == 0) return out;
+  if (pay.is_cuda()) {
+    launch_mx6_dequantize_blocks(pay.data_ptr(), sc.data_ptr(),
+                                 out.data_ptr(), P, rows, row_elems, dt,
+                                 current_gpu_stream(pay));
+    return out;
+  }
+  const int64_t L = rows * row_elems;
+  const int64_t Gb = (L + 31) / 32;
+  auto pv = pay.view({P, Gb, 24});
+  auto sv = sc.view({P, Gb});
+  for (int r = 0; r < P; ++r) {
+    auto d = mx6_dequantize_groups(pv[r], sv[r]).view({-1});
+    out.select(1, r).copy_(
+        d.narrow(0, 0, L).to(dtype).view({rows, row_elems}));
+  }
+  return out;
+}
+
+// mx8_allgather on the mxfp6 wire: one quantize, the two byte allgathers
+// (payload [P][Gb*24], scales [P][Gb]), the fused tail. The wire carries
+// (P-1)*25*ceil(L/32) bytes received per rank.
+Tensor mx6_allgather(Transport& tr, const Tensor& in, int64_t rows,
+                     int64_t row_elems) {
+  const int P = tr.size();
+  const int64_t Gb = (rows * row_elems + 31) / 32;
+  auto q = mx6_quantize(in.view({-1}));
+  auto bopts = in.options().dtype(at::kByte);
+  auto all_pay = at::empty({(int64_t)P * Gb * 24}, bopts);
+  auto all_sc = at::empty({(int64_t)P * Gb}, bopts);
+  tr.allgather_equal(q.first, all_pay);
+  tr.allgather_equal(q.second, all_sc);
+  return mx6_dequantize_blocks(all_pay, all_sc, P, rows, row_elems,
+                               in.scalar_type());
+}
+
 // `in`: contiguous, rows*P*row_elems elements seen as [rows, P, row_elems]
 // -> (payload [P, Gb*32], scales [P, Gb]), Gb = ceil(rows*row_elems/32).
 // The all-to-all head, normative here: block p is mx8_quantize of the
@@ -2867,11 +3023,15 @@ struct AllgatherCompressedBackward : public M4ANode {
 } // namespace
 
 namespace {
-// Both wires; `fp4` selects mxfp4 (the backward is the mxfp8 reduce-scatter
-// either way: gradients do not go to fp4).
+// The three wires (the backward is the mxfp8 reduce-scatter for each:
+// gradients do not go to fp6 or fp4).
+enum class AllgatherWire { kMx8, kMx6, kMx4 };
+
 Tensor allgather_compressed(Communicator& comm, const Tensor& input,
-                            int64_t axis, bool fp4) {
-  const char* who = fp4 ? "AllgatherCompressedFp4" : "AllgatherCompressed";
+                            int64_t axis, AllgatherWire wire) {
+  const char* who = wire == AllgatherWire::kMx4   ? "AllgatherCompressedFp4"
+                    : wire == AllgatherWire::kMx6 ? "AllgatherCompressedFp6"
+                                                  : "AllgatherCompressed";
   check_mx8_input(who, input);
   axis = at::maybe_wrap_dim(axis, input.dim());
   auto make_grad_fn = [&](auto comm) {
@@ -2880,7 +3040,7 @@ Tensor allgather_compressed(Communicator& comm, const Tensor& input,
   auto body = [&](Transport& tr, const Tensor& in,
                   const DeviceStager&) -> Tensor {
     const int P = tr.size();
-    // full path: quantize, 1-rank allgather, mx8/mx4_dequantize_blocks
+    // full path: quantize, 1-rank allgather, mx8/mx6/mx4_dequantize_blocks
     if (world1_shortcut(tr, in)) return fast_clone(in);
     debug_check_axis_collective(comm.group_name(), who, in, {axis}, {axis});
     const auto g = axis_geom(in, axis);
@@ -2895,8 +3055,13 @@ Tensor allgather_compressed(Communicator& comm, const Tensor& input,
     auto outsizes = in.sizes().vec();
     outsizes[axis] = g.axis * P;
     if (in.numel() == 0) return at::empty(outsizes, in.options());
-    return (fp4 ? mx4_allgather(tr, in, g.before, g.axis * g.after)
-                : mx8_allgather(tr, in, g.before, g.axis * g.after))
+    const int64_t row_elems = g.axis * g.after;
+    return (wire == AllgatherWire::kMx4   ? mx4_allgather(tr, in, g.before,
+                                                          row_elems)
+            : wire == AllgatherWire::kMx6 ? mx6_allgather(tr, in, g.before,
+                                                          row_elems)
+                                          : mx8_allgather(tr, in, g.before,
+                                                          row_elems))
         .view(outsizes);
   };
   return collective_frame(comm, input, make_grad_fn, body);
@@ -2904,12 +3069,17 @@ Tensor allgather_compressed(Communicator& comm, const Tensor& input,
 } // namespace
 
 Tensor Communicator::AllgatherCompressed(const Tensor& input, int64_t axis) {
-  return allgather_compressed(*this, input, axis, false);
+  return allgather_compressed(*this, input, axis, AllgatherWire::kMx8);
 }
 
 Tensor Communicator::AllgatherCompressedFp4(const Tensor& input,
                                             int64_t axis) {
-  return allgather_compressed(*this, input, axis, true);
+  return allgather_compressed(*this, input, axis, AllgatherWire::kMx4);
+}
+
+Tensor Communicator::AllgatherCompressedFp6(const Tensor& input,
+                                            int64_t axis) {
+  return allgather_compressed(*this, input, axis, AllgatherWire::kMx6);
 }
 
 // ---------------------------------------------------------------------------
@@ -4519,6 +4689,56 @@ Tensor debug_mx4_dequantize_blocks(const Tensor& payload,
   check_canary_out("debug_mx4_dequantize_blocks", *out, total, dtype,
                    pin.device(), "rows*P*row_elems");
   return mx4_dequantize_blocks(
+      pin, sin, (int)P, rows, row_elems, dtype,
+      out->narrow(0, 0, total).view({rows, P, row_elems}));
+}
+
+std::tuple<Tensor, Tensor> debug_mx6_quantize(
+    const Tensor& x, const c10::optional<Tensor>& payload_out,
+    const c10::optional<Tensor>& scales_out) {
+  auto flat = x.contiguous().view({-1});
+  TORCH_CHECK(payload_out.has_value() == scales_out.has_value(),
+              "debug_mx6_quantize: payload_out and scales_out go together");
+  if (!payload_out.has_value()) {
+    auto ps = mx6_quantize(flat);
+    return std::make_tuple(ps.first, ps.second);
+  }
+  const int64_t G = (flat.numel() + 31) / 32;
+  auto ok = [&](const Tensor& t, int64_t need) {
+    return t.dim() == 1 && t.is_contiguous() &&
+           t.scalar_type() == at::kByte && t.numel() >= need &&
+           t.device() == flat.device();
+  };
+  TORCH_CHECK(ok(*payload_out, G * 24) && ok(*scales_out, G),
+              "debug_mx6_quantize: payload_out and scales_out must be flat "
+              "contiguous uint8 tensors with at least G*24 and G elements");
+  auto ps = mx6_quantize(flat, payload_out->narrow(0, 0, G * 24),
+                         scales_out->narrow(0, 0, G));
+  return std::make_tuple(ps.first, ps.second);
+}
+
+Tensor debug_mx6_dequantize_blocks(const Tensor& payload,
+                                   const Tensor& scales, int64_t P,
+                                   int64_t rows, int64_t row_elems,
+                                   at::ScalarType dtype,
+                                   const c10::optional<Tensor>& out) {
+  TORCH_CHECK(payload.scalar_type() == at::kByte &&
+                  scales.scalar_type() == at::kByte && P >= 1 && P <= 65535 &&
+                  rows >= 1 && row_elems >= 1 &&
+                  scales.numel() == P * ((rows * row_elems + 31) / 32) &&
+                  payload.numel() == scales.numel() * 24,
+              "debug_mx6_dequantize_blocks expects uint8 payload [P, Gb*24] "
+              "and scales [P, Gb], Gb = ceil(rows*row_elems/32), 1..65535 "
+              "blocks");
+  auto pin = payload.contiguous().view({-1});
+  auto sin = scales.contiguous().view({-1});
+  if (!out.has_value()) {
+    return mx6_dequantize_blocks(pin, sin, (int)P, rows, row_elems, dtype);
+  }
+  const int64_t total = rows * P * row_elems;
+  check_canary_out("debug_mx6_dequantize_blocks", *out, total, dtype,
+                   pin.device(), "rows*P*row_elems");
+  return mx6_dequantize_blocks(
       pin, sin, (int)P, rows, row_elems, dtype,
       out->narrow(0, 0, total).view({rows, P, row_elems}));
 }

@@ -82,6 +82,10 @@ struct Communicator : torch::CustomClassHolder {
   // what AllgatherCompressed(..., wire="mxfp4") calls. Semantics, checks and
   // the backward (ReducescatterCompressed on the mxfp8 wire) are unchanged.
   at::Tensor AllgatherCompressedFp4(const at::Tensor& input, int64_t axis);
+  // The same op over the mxfp6 wire (e2m3 codes, 25/32 byte per element):
+  // what AllgatherCompressed(..., wire="mxfp6-e2m3") calls, otherwise as
+  // AllgatherCompressedFp4.
+  at::Tensor AllgatherCompressedFp6(const at::Tensor& input, int64_t axis);
   // Equal-count, two-axis all-to-all over the mxfp8 wire (MI355X
   // extension): the scatter axis is split into GetSize() equal blocks, a
   // fused gfx950 kernel quantizes every block in place (groups of 32 that
@@ -284,6 +288,18 @@ std::tuple<at::Tensor, at::Tensor> debug_mx4_quantize(
 // mxfp4 allgather tail: payload P*Gb*16 bytes, scales P*Gb bytes,
 // Gb = ceil(rows*row_elems/32) -> [rows, P, row_elems] of dtype
 at::Tensor debug_mx4_dequantize_blocks(const at::Tensor& payload,
+                                       const at::Tensor& scales, int64_t P,
+                                       int64_t rows, int64_t row_elems,
+                                       at::ScalarType dtype,
+                                       const c10::optional<at::Tensor>& out);
+// mxfp6: x (any shape, flattened) -> (payload [G*24], scales [G]); with the
+// two outs (flat uint8, at least that long) the bytes are written in place.
+std::tuple<at::Tensor, at::Tensor> debug_mx6_quantize(
+    const at::Tensor& x, const c10::optional<at::Tensor>& payload_out,
+    const c10::optional<at::Tensor>& scales_out);
+// mxfp6 allgather tail: payload P*Gb*24 bytes, scales P*Gb bytes,
+// Gb = ceil(rows*row_elems/32) -> [rows, P, row_elems] of dtype
+at::Tensor debug_mx6_dequantize_blocks(const at::Tensor& payload,
                                        const at::Tensor& scales, int64_t P,
                                        int64_t rows, int64_t row_elems,
                                        at::ScalarType dtype,

@@ -6,11 +6,13 @@ reduce-scatters; the optimizer and gradient clipping operate on the 1/P
 shards.
 
 Run: torchrun --standalone --local-addr 127.0.0.1 --nproc-per-node 2 \
-        examples/fsdp_training.py [--param-compression mxfp8|mxfp4] \
+        examples/fsdp_training.py \
+        [--param-compression mxfp8|mxfp6-e2m3|mxfp4] \
         [--grad-compression mxfp8]
 
 --param-compression mxfp8 gathers the parameters over the block-scaled fp8
 wire (AllgatherCompressed), mxfp4 over its fp4 wire (17/32 byte per element),
+mxfp6-e2m3 over the fp6 wire between them (25/32 byte per element),
 --grad-compression mxfp8 reduces the gradients
 over it (ReducescatterCompressed); the optimizer's shards stay full
 precision either way.
@@ -28,8 +30,8 @@ from mpi4torch_amd.parallel import FullyShardedDataParallel
 from mpi4torch_amd.utils import clip_grad_norm_sharded
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--param-compression", choices=["mxfp8", "mxfp4"],
-                default=None)
+ap.add_argument("--param-compression",
+                choices=["mxfp8", "mxfp6-e2m3", "mxfp4"], default=None)
 ap.add_argument("--grad-compression", choices=["mxfp8"], default=None)
 args = ap.parse_args()
 

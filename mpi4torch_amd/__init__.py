@@ -256,9 +256,10 @@ class MPI_Communicator:
 
     def AllgatherCompressed(self, tensor: torch.Tensor, axis: int = 0,
                             wire: str = "mxfp8") -> torch.Tensor:
-        """Allgather that travels as block-scaled fp8 or fp4 (MI355X
+        """Allgather that travels as block-scaled fp8, fp6 or fp4 (MI355X
         extension): the FSDP parameter primitive over the mxfp8 wire, or
-        with ``wire="mxfp4"`` over the mxfp4 wire.
+        with ``wire="mxfp6-e2m3"`` / ``wire="mxfp4"`` over the mxfp6 or
+        mxfp4 wire.
 
         Every rank's tensor (float32, bfloat16 or float16) must have the
         same size on ``axis`` (Allgather handles variable counts); the
@@ -286,14 +287,24 @@ class MPI_Communicator:
         and the backward still travels as mxfp8. It suits values that are
         re-sent from a full-precision master copy, such as FSDP parameters;
         the codec rule is in doc/kernels.md.
+
+        ``wire="mxfp6-e2m3"`` sits between the two: an OCP e2m3 code of 6
+        bits, the three mantissa bits of e4m3 under the same group scale,
+        25/32 byte per element, 0.758 of the mxfp8 wire. The large elements
+        of a group keep e4m3's grid; only those more than a factor of about
+        4 to 8 below the group's maximum move to a fixed step. Semantics and
+        backward are again unchanged. (``"mxfp6"`` alone is refused: MX
+        defines a second 6-bit format, e3m2, which this op does not have.)
         """
         if wire == "mxfp8":
             return self._comm.AllgatherCompressed(tensor, axis)
+        if wire == "mxfp6-e2m3":
+            return self._comm.AllgatherCompressedFp6(tensor, axis)
         if wire == "mxfp4":
             return self._comm.AllgatherCompressedFp4(tensor, axis)
         raise ValueError(
-            "mpi4torch_amd: AllgatherCompressed: wire must be 'mxfp8' or "
-            "'mxfp4', got '" + wire + "'")
+            "mpi4torch_amd: AllgatherCompressed: wire must be 'mxfp8', "
+            "'mxfp6-e2m3' or 'mxfp4', got '" + wire + "'")
 
     def AlltoallCompressed(self, tensor: torch.Tensor, gatheraxis: int,
                            scatteraxis: int) -> torch.Tensor:

@@ -24,7 +24,9 @@ compresses nothing): ``param_compression="mxfp8"`` gathers every unit's
 parameters with AllgatherCompressed (block-scaled fp8 wire, 33/32 byte per
 element); ``param_compression="mxfp4"`` does so on the op's fp4 wire (e2m1
 nibbles, 17/32 byte per element), which costs the optimizer nothing because
-the master shard never travels. The master shard keeps full precision; every
+the master shard never travels; ``param_compression="mxfp6-e2m3"`` is the
+wire between them (e2m3 codes, 25/32 byte per element, e4m3's three mantissa
+bits for the large elements of every group). The master shard keeps full precision; every
 rank, the owner included, computes with the same dequantized parameters. That
 op is blocking
 (stream-ordered on GPU, host-blocking on gloo) and has no non-blocking
@@ -192,10 +194,10 @@ class FullyShardedDataParallel(torch.nn.Module):
                  grad_compression: Optional[str] = None,
                  compression_seed: int = 0):
         super().__init__()
-        if param_compression not in (None, "mxfp8", "mxfp4"):
+        if param_compression not in (None, "mxfp8", "mxfp6-e2m3", "mxfp4"):
             raise ValueError(
-                "mpi4torch_amd FSDP: param_compression must be None, 'mxfp8' "
-                f"or 'mxfp4', got {param_compression!r}")
+                "mpi4torch_amd FSDP: param_compression must be None, 'mxfp8', "
+                f"'mxfp6-e2m3' or 'mxfp4', got {param_compression!r}")
         if grad_compression not in (None, "mxfp8", "mxfp8-sr"):
             raise ValueError(
                 "mpi4torch_amd FSDP: grad_compression must be None, 'mxfp8' "

@@ -2,6 +2,7 @@ from .timing import (CollectiveTimer, algbw_gbps, busbw_gbps,
                      mxfp8_wire_bytes, mxfp8_reducescatter_wire_bytes,
                      mxfp8_allgather_wire_bytes,
                      mxfp4_allgather_wire_bytes,
+                     mxfp6_allgather_wire_bytes,
                      alltoall_compressed_wire_bytes,
                      mxfp8_alltoall_pairwise_wire_bytes)
 from .tracing import trace, TracedCommunicator, TraceRecord
@@ -17,6 +18,7 @@ __all__ = [
     "mxfp8_reducescatter_wire_bytes",
     "mxfp8_allgather_wire_bytes",
     "mxfp4_allgather_wire_bytes",
+    "mxfp6_allgather_wire_bytes",
     "alltoall_compressed_wire_bytes",
     "mxfp8_alltoall_pairwise_wire_bytes",
     "trace",

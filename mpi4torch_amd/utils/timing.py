@@ -59,6 +59,13 @@ def mxfp4_allgather_wire_bytes(numel: int, world: int) -> int:
     return (world - 1) * 17 * ((numel + 31) // 32)
 
 
+def mxfp6_allgather_wire_bytes(numel: int, world: int) -> int:
+    """mxfp8_allgather_wire_bytes for
+    ``AllgatherCompressed(wire="mxfp6-e2m3")``: 24 payload bytes of e2m3
+    codes plus the scale byte per group of 32, 25/32 byte per element."""
+    return (world - 1) * 25 * ((numel + 31) // 32)
+
+
 def alltoall_compressed_wire_bytes(numel: int, world: int) -> int:
     """Bytes one rank sends in AlltoallCompressed of its own tensor of
     ``numel`` elements over ``world`` ranks: every other rank's block of

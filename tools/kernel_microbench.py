@@ -14,6 +14,7 @@ reported GB/s counts actual bytes touched. Run on an MI355X box:
     python tools/kernel_microbench.py --mx8-weighted            # only that part
     python tools/kernel_microbench.py --mx8-sr    # stochastic rounding vs nearest
     python tools/kernel_microbench.py --mx4       # mxfp4 kernels vs mxfp8 siblings
+    python tools/kernel_microbench.py --mx6       # mxfp6 kernels vs both siblings
 
 The mxfp8 section times the three codec kernels and, in the same run and
 alternating with it, the sibling fp8_reduce kernel at the same P and n, so
@@ -746,6 +747,74 @@ def mx4_section(repeats=5):
             del out
         del sc, pay8, pay4
 
+
+def mx6_section(repeats=5):
+    """The mxfp6 kernels against both siblings at equal N, the three
+    alternating in the same run, on mx4_section's cases: quantize at 256Mi
+    elements, dequantize_blocks at P = 8 blocks of 32Mi elements as (a) one
+    row, (b) rows of 320 elements, (c) one odd row (the general twins). Bytes
+    are what each kernel moves: N*esize on the tensor side plus 33N/32 (mx8),
+    25N/32 (mx6) or 17N/32 (mx4)."""
+    C = m._C
+    med = lambda v: sorted(v)[len(v) // 2]
+
+    def versus(tag, fns, tensor_bytes, n):
+        t = {k: [] for k in fns}
+        for _ in range(repeats):
+            for k, fn in fns.items():
+                t[k].append(timeit(fn))
+        for (k, v), wire in zip(t.items(), (33, 25, 17)):
+            nbytes = tensor_bytes + wire * n // 32
+            print(f"{k + '_' + tag:40s} {med(v)*1e3:9.1f} us  "
+                  f"{nbytes/med(v)/1e6:8.1f} GB/s  (min {min(v)*1e3:.1f} max "
+                  f"{max(v)*1e3:.1f} us, {repeats} repeats)", flush=True)
+        t8 = t["mx8"]
+        print(f"  mx6 / mx8 time ratio {med(t['mx6'])/med(t8):.3f}, mx4 / mx8 "
+              f"{med(t['mx4'])/med(t8):.3f}, mx8 spread "
+              f"{min(t8)/med(t8):.3f}-{max(t8)/med(t8):.3f}", flush=True)
+
+    NQ = 256 << 20
+    for dtype, tag in ((torch.float32, "fp32"), (torch.bfloat16, "bf16")):
+        x = torch.randn(NQ, device="cuda")
+        x.view(-1, 32).mul_(torch.rand(NQ // 32, 1, device="cuda"))
+        x = x.to(dtype)
+        versus(f"quantize {tag} N={NQ>>20}Mi",
+               {"mx8": lambda: C._mx8_quantize(x),
+                "mx6": lambda: C._mx6_quantize(x),
+                "mx4": lambda: C._mx4_quantize(x)}, NQ * x.element_size(), NQ)
+        del x
+    Lb = 32 << 20
+    for rows, row_elems, what in ((1, Lb, "a: one row"),
+                                  (Lb // 320, 320, "b: rows of 320"),
+                                  (1, Lb + 1, "c: odd row, twins")):
+        L = rows * row_elems
+        Gb = (L + 31) // 32
+        sc = torch.randint(120, 135, (P, Gb), dtype=torch.uint8, device="cuda")
+        pay8 = torch.randint(0, 0x7e, (P, Gb * 32), dtype=torch.uint8,
+                             device="cuda")
+        pay6 = torch.randint(0, 256, (P, Gb * 24), dtype=torch.uint8,
+                             device="cuda")
+        pay4 = torch.randint(0, 256, (P, Gb * 16), dtype=torch.uint8,
+                             device="cuda")
+        for dtype, tag in ((torch.float32, "fp32"), (torch.bfloat16, "bf16")):
+            es = torch.empty((), dtype=dtype).element_size()
+            out = torch.empty(rows * P * row_elems, dtype=dtype, device="cuda")
+            versus(f"dequantize_blocks {tag} ({what})",
+                   {"mx8": lambda: C._mx8_dequantize_blocks(
+                       pay8, sc, rows, row_elems, dtype, out=out),
+                    "mx6": lambda: C._mx6_dequantize_blocks(
+                        pay6, sc, P, rows, row_elems, dtype, out=out),
+                    "mx4": lambda: C._mx4_dequantize_blocks(
+                        pay4, sc, P, rows, row_elems, dtype, out=out)},
+                   P * L * es, P * Gb * 32)
+            del out
+        del sc, pay8, pay6, pay4
+
+
+if "--mx6" in sys.argv:
+    mx6_section()
+    dist.destroy_process_group()
+    sys.exit(0)
 
 if "--mx4" in sys.argv:
     mx4_section()
